@@ -21,9 +21,21 @@ Workloads (--workload; the default is the headline line):
       strong scaling), generated on the device; per-GPU and aggregate
       Mmsgs/s, every shard's base in the global send buffer from one
       all_gather of the byte totals (no data-path collective).
-Unless --c4-leg off, a run of c0..c3 also runs the configs[4] leg after the
-headline and reports it as `configs4` in the same JSON line (so the
-driver's 1/2/4/8-GPU runs record configs[4] at every N).
+
+A run does the headline only: it sets up the batch, runs --warmup steps,
+times --steps steps between two events, checks the last step's outputs on
+the device and prints one JSON line (`value`, `ms_per_step`, ...).
+--dump-outputs DIR also writes what the last timed step computed as
+DIR/<name>.npy (dump_outputs: the inputs are seeded, so two builds given the
+same arguments write comparable files).
+
+--full adds everything else, each leg still switched by its own option: the
+per-kernel breakdown pass, the dominant kernel's launches timed by events
+inside the timed region and the event-free pass (`roofline`,
+`kernels_breakdown_pass`), the cache legs, the PCIe-inclusive legs, the
+vectored-encode leg of c1, the CPU baseline, and, unless --c4-leg off, after
+a c0..c3 headline the configs[4] leg, reported as `configs4` in the same
+JSON line (so the driver's 1/2/4/8-GPU runs record configs[4] at every N).
 
 Launch: `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the
 environment starts N ranks itself (python -m torch.distributed.run, one
@@ -31,9 +43,9 @@ process per GPU, as a child process before any GPU call) and exits with
 their status; under torch.distributed.run (WORLD_SIZE set) every rank
 checks that the world size equals --gpus.
 
-Besides the device-resident `value`, every run also times the PCIe-inclusive
-rate (pinned host inputs -> H2D -> kernels -> D2H of the outputs), reported
-as `pcie_inclusive` (never as `value`).
+Besides the device-resident `value`, every --full run also times the
+PCIe-inclusive rate (pinned host inputs -> H2D -> kernels -> D2H of the
+outputs), reported as `pcie_inclusive` (never as `value`).
 """
 import argparse
 import json
@@ -58,6 +70,13 @@ def parse(argv=None):
                     help="GPUs, one rank each (default: WORLD_SIZE or 1); N > 1 without WORLD_SIZE spawns N ranks")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline also run every other leg: per-kernel breakdown and roofline, cache "
+                         "legs, PCIe-inclusive legs, the vectored-encode and configs[4] legs, the CPU baseline "
+                         "(each still switched by its own option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32 / "
+                         "float64; a fixed, seeded sample of the larger arrays)")
     ap.add_argument("--workload", choices=["c0", "c1", "c2", "c3", "c4"], default="c1")
     ap.add_argument("--records", type=int, default=None, help="records per GPU (c0-c3) / in total (c4)")
     ap.add_argument("--c4-leg", choices=["on", "off"], default="on",
@@ -97,7 +116,12 @@ def parse(argv=None):
                     help="pin the decode's first-round policy for every codec of the run (A/B measurements)")
     ap.add_argument("--variant", type=lambda s: int(s, 0), default=0,
                     help="kernel variant bits (onc_codec_options.variant; A/B measurements only)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:
+        # the headline only: set up, warm up, time the steps, print the line
+        args.c4_leg = args.iov_leg = args.cache_leg = "off"
+        args.no_pcie = args.no_cpu_baseline = True
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -1076,11 +1100,34 @@ class Timing:
     bracketed by barrier + synchronize on both sides, the dominant kernel's
     launches of every K//5-th step timed by HIP events on the codec's stream
     (hipExtLaunchKernelGGL start/stop events: the dispatch's own timestamps);
-    and an event-free pass of the same K steps."""
+    and an event-free pass of the same K steps.
+    full=False (a run without --full): W warmup steps and the timed region
+    only, no launch timed by events — the breakdown pass, the per-launch
+    events and the event-free pass are runs of their own."""
 
-    def __init__(self, torch, R, codec, step, steps, warmup, barrier, codecs=None, drain=None):
+    def __init__(self, torch, R, codec, step, steps, warmup, barrier, codecs=None, drain=None, full=True):
         codecs = codecs or [codec]
         drain = drain or (lambda: None)
+        if not full:
+            for _ in range(warmup):
+                step()
+            torch.cuda.synchronize()
+            barrier()
+            torch.cuda.synchronize()
+            ev0 = torch.cuda.Event(enable_timing=True)
+            ev1 = torch.cuda.Event(enable_timing=True)
+            t_wall0 = time.perf_counter()
+            ev0.record()
+            for _ in range(steps):
+                step()
+            drain()
+            ev1.record()
+            torch.cuda.synchronize()
+            barrier()
+            self.wall_s = time.perf_counter() - t_wall0
+            self.ms = self.ms_clean = ev0.elapsed_time(ev1)
+            self.steps_n = steps
+            return
 
         def stats():
             tot = {}
@@ -1258,9 +1305,88 @@ def agree(torch, dist, dev, ok):
 
 
 # ---------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------
+DUMP_SEED = 0x0DC0DE
+DUMP_RECORDS = 16384           # records sampled from a larger batch
+DUMP_WIRE_BYTES = 1 << 21      # byte positions sampled from a larger buffer
+
+
+def dump_outputs(dirpath, torch, L, rank, n, wire=None, wire_bytes=0, rec_off=None, enc_status=None, dec=None,
+                 hdr_out=None, hdr_total=0, iov=None, iov_status=None, iov_tot=None, extra=None):
+    """What the timed step left in its output buffers, as DIR/<name>.npy
+    (rank r > 0: <name>.rank<r>.npy): integers that fit a float32 exactly
+    (bytes) as float32, the others as float64. Batches beyond DUMP_RECORDS
+    records are sampled — the same seeded record indices (`sample_records`)
+    for every per-record array — and byte buffers beyond DUMP_WIRE_BYTES at
+    seeded positions (`*_sample_positions`), so two builds given the same
+    arguments write comparable files (43 MB at most). Contents a decode
+    leaves undefined are written as zero: aux words of OK records, and the
+    AUTH_UNIX slots no decoded auth references (dec_unix_params is the
+    (cred, verf) parameter pair of each record, the descriptor's refs zeroed:
+    layout.resolve_unix's form)."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    sfx = f".rank{rank}" if rank else ""
+
+    def save(name, a, dt):
+        np.save(os.path.join(dirpath, f"{name}{sfx}.npy"), np.ascontiguousarray(a).astype(dt))
+
+    idx = np.arange(n, dtype=np.int64) if n <= DUMP_RECORDS else np.sort(rng.choice(n, DUMP_RECORDS, replace=False))
+    save("sample_records", idx, np.float64)
+
+    def rows(t, width=1):
+        """Rows `idx` of a device array of n rows of `width` elements."""
+        return t[: n * width].view(n, width)[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+
+    def sampled_bytes(name, buf, nbytes):
+        if nbytes <= DUMP_WIRE_BYTES:
+            save(name, buf[:nbytes].cpu().numpy(), np.float32)
+            return
+        pos = np.sort(rng.integers(0, nbytes, DUMP_WIRE_BYTES, dtype=np.int64))
+        save(name + "_sample_positions", pos, np.float64)
+        save(name, buf[torch.from_numpy(pos).to(buf.device)].cpu().numpy(), np.float32)
+
+    if n == 0:
+        return
+    if wire is not None:
+        sampled_bytes("wire", wire, wire_bytes)
+    if rec_off is not None:
+        save("rec_off", rows(rec_off).reshape(-1), np.float64)
+        save("rec_off_end", rec_off[n:n + 1].cpu().numpy(), np.float64)
+    if enc_status is not None:
+        save("enc_status", rows(enc_status).reshape(-1), np.float64)
+    if dec is not None:
+        msgs = rows(dec.msgs, 64).copy().view(L.MSG_DTYPE).reshape(-1)
+        status = rows(dec.status).reshape(-1)
+        params = np.zeros((len(idx), 2, L.UNIX_DTYPE.itemsize), np.uint8)
+        slots = dec.unix.view(-1, L.UNIX_DTYPE.itemsize)
+        for k, (f, mask) in enumerate(zip(("cred", "verf"), L.unix_used(msgs, status))):
+            sel = np.nonzero(mask)[0]
+            if sel.size:
+                ref = np.clip(msgs[f + "_ref"][sel].astype(np.int64), 0, slots.shape[0] - 1)
+                params[sel, k] = slots[torch.from_numpy(ref).to(slots.device)].cpu().numpy()
+                msgs[f + "_ref"][sel] = 0
+        save("dec_msgs", msgs.view(np.uint8).reshape(len(idx), 64), np.float32)
+        save("dec_unix_params", params.reshape(len(idx), -1), np.float32)
+        save("dec_status", status, np.float64)
+        for name, t in (("dec_aux0", dec.aux0), ("dec_aux1", dec.aux1)):
+            save(name, np.where(status != 0, rows(t).reshape(-1).view(np.uint32), 0), np.float64)
+    if hdr_out is not None:
+        sampled_bytes("iov_headers", hdr_out, hdr_total)
+        e = rows(iov, 32).copy().view(L.IOV_DTYPE).reshape(-1)
+        save("iov_entries", np.stack([e[f].astype(np.float64) for f in L.IOV_DTYPE.names], 1), np.float64)
+        save("iov_status", rows(iov_status).reshape(-1), np.float64)
+        save("iov_totals", iov_tot.cpu().numpy(), np.float64)
+    for name, t in (extra or {}).items():
+        save(name, t.cpu().numpy(), np.float64)
+
+
+# ---------------------------------------------------------------------------
 # configs[4]: 64M records in total, sharded over the ranks (strong scaling)
 # ---------------------------------------------------------------------------
-def run_c4(args, torch, R, S, SH, L, dist, rank, world, local_rank, total, mode, steps, warmup):
+def run_c4(args, torch, R, S, SH, L, dist, rank, world, local_rank, total, mode, steps, warmup, dump_dir=None):
     dev = torch.device("cuda", local_rank)
     lo, hi = SH.shard_bounds(total, world, rank)
     n = hi - lo
@@ -1288,11 +1414,14 @@ def run_c4(args, torch, R, S, SH, L, dist, rank, world, local_rank, total, mode,
         if dist is not None:
             dist.barrier()
 
-    tm = Timing(torch, R, codec, step, steps, warmup, barrier)
+    tm = Timing(torch, R, codec, step, steps, warmup, barrier, full=args.full)
     t = torch.tensor([tm.ms, tm.ms_clean], dtype=torch.float64, device=cdev(dev))
     if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     ms_max, ms_clean_max = float(t[0]), float(t[1])
+    if dump_dir:
+        dump_outputs(dump_dir, torch, L, rank, n, wire=out, wire_bytes=local_bytes, rec_off=rec_off,
+                     enc_status=enc_status, dec=dec)
 
     # validation of the last step (device side) + global placement of the shard
     ok = int((enc_status[:n] != 0).sum()) == 0 and int((dec.status[:n] != 0).sum()) == 0
@@ -1314,7 +1443,6 @@ def run_c4(args, torch, R, S, SH, L, dist, rank, world, local_rank, total, mode,
     ms_per_step = ms_max / steps
     sum_W, sum_H = local_bytes, n * C4_H
     step_alg = 2 * sum_W + 2 * sum_H + 4 * n
-    traffic, tsrc = load_traffic(None, "c4", n, tm.dom)
     res = {
         "metric": METRIC, "value": total / (ms_per_step / 1e3) / 1e6, "unit": "Mmsgs/s", "n_gpus": world,
         "steps": steps, "warmup": warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
@@ -1327,14 +1455,16 @@ def run_c4(args, torch, R, S, SH, L, dist, rank, world, local_rank, total, mode,
                    "parallelism": f"record-sharded x{world} (no collective on the data path)"},
         "per_gpu": per_gpu,
         "ms_per_step_without_kernel_events": ms_clean_max / steps,
-        "roofline": roofline(tm, n, sum_W, sum_H, step_alg, ms_per_step, traffic, tsrc),
-        "kernels_breakdown_pass": breakdown_dict(tm, n, sum_W, sum_H),
         "global_send_buffer": {"shard_bytes": totals, "bases": [int(b) for b in bases], "total": grand,
                                "note": "exclusive scan of one all_gather'ed int64 per rank "
                                        "(shard.allgather_totals + exclusive_bases)"},
         "validated": ok,
         "wall_s_timed_region": tm.wall_s,
     }
+    if args.full:
+        traffic, tsrc = load_traffic(None, "c4", n, tm.dom)
+        res["roofline"] = roofline(tm, n, sum_W, sum_H, step_alg, ms_per_step, traffic, tsrc)
+        res["kernels_breakdown_pass"] = breakdown_dict(tm, n, sum_W, sum_H)
     codec.close()
     del db, out, rec_off, enc_status, dec
     torch.cuda.synchronize()
@@ -1499,11 +1629,21 @@ def run_main(args, torch, R, S, SH, L, dist, rank, world, local_rank, mode):
         if dist is not None:
             dist.barrier()
 
-    tm = Timing(torch, R, codec, step, args.steps, args.warmup, barrier)
+    tm = Timing(torch, R, codec, step, args.steps, args.warmup, barrier, full=args.full)
     t = torch.tensor([tm.ms, tm.ms_clean], dtype=torch.float64, device=cdev(dev))
     if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     ms_max, ms_clean_max = float(t[0]), float(t[1])
+    if args.dump_outputs:
+        if args.iov:
+            dump_outputs(args.dump_outputs, torch, L, rank, n, hdr_out=hdr_out, hdr_total=iov_hdr_total, iov=iov,
+                         iov_status=iov_status, iov_tot=iov_tot)
+        elif wl == "c2":
+            dump_outputs(args.dump_outputs, torch, L, rank, n, rec_off=dec_off, dec=dec,
+                         extra={"frame_result": frame_res} if args.frame else None)
+        else:
+            dump_outputs(args.dump_outputs, torch, L, rank, n, wire=out, wire_bytes=total_bytes, rec_off=rec_off,
+                         enc_status=enc_status, dec=dec)
 
     # The other cache state, next to the primary line (SURVEY §7 "Cache
     # effects"): c2 warm (or cold); for the loopbacks, the decode alone on the
@@ -1639,7 +1779,6 @@ def run_main(args, torch, R, S, SH, L, dist, rank, world, local_rank, mode):
         step_alg = ALG_PER_LAUNCH["iov_len_kernel"](n, sum_W, sum_H) + ALG_PER_LAUNCH["iov_emit_kernel"](n, sum_W, sum_H)
     else:
         step_alg = (2 * sum_H + 4 * n) + (0 if wl == "c2" else 2 * sum_W)
-    traffic, tsrc = load_traffic(args.traffic_json, wl, n, tm.dom)
     per_gpu = gather_per_gpu(torch, dist, dev, rank, n, tm.ms / steps, tm.ms_clean / steps)
     for r, row in enumerate(per_gpu):
         row["global_base"] = int(bases[r])
@@ -1661,18 +1800,20 @@ def run_main(args, torch, R, S, SH, L, dist, rank, world, local_rank, mode):
                    "decode_mode": args.mode,
                    "cache": (args.cache if wl == "c2" else "loopback"), "cache_note": cache_note,
                    "parallelism": f"record-sharded x{world} (no collective)"},
-        "cache_legs": cache_legs,
         "wire_GiB_per_s": wire_gibs,
         "ms_per_step_without_kernel_events": ms_clean_max / steps,
         "step_alg_GBs": step_alg * world / (ms_per_step / 1e3) / 1e9,
-        "roofline": roofline(tm, n, sum_W, sum_H, step_alg, ms_per_step, traffic, tsrc),
         "per_gpu": per_gpu,
         "global_send_buffer": {"shard_bytes": totals, "bases": [int(b) for b in bases], "total": grand},
-        "kernels_breakdown_pass": breakdown_dict(tm, n, sum_W, sum_H),
-        "pcie_inclusive": pcie,
         "validated": ok,
         "wall_s_timed_region": tm.wall_s,
     }
+    if args.full:
+        traffic, tsrc = load_traffic(args.traffic_json, wl, n, tm.dom)
+        result.update({"cache_legs": cache_legs,
+                       "roofline": roofline(tm, n, sum_W, sum_H, step_alg, ms_per_step, traffic, tsrc),
+                       "kernels_breakdown_pass": breakdown_dict(tm, n, sum_W, sum_H),
+                       "pcie_inclusive": pcie})
     if args.iov:
         result["config"]["header_bytes_per_gpu"] = sum_H
         result["config"].pop("parsed_bytes_per_gpu", None)
@@ -1687,7 +1828,7 @@ def run_main(args, torch, R, S, SH, L, dist, rank, world, local_rank, mode):
             # N > 1: rank 0 times it after every GPU leg of every rank (main()),
             # so no rank's timed region shares the host with it
             result["_cpu_pending"] = (wl, hb, prefix, wire_np, off_np, mode)
-    elif rank == 0:
+    elif rank == 0 and args.full:
         result["cpu_baseline"] = None
     codec.close()
     del db, out, rec_off, dec_off, dec, enc_status, rec_len
@@ -1731,7 +1872,8 @@ def finish(args, result, pending, dist, rank, world):
     then rank 0 prints the one JSON line."""
     if dist is not None:
         dist.barrier()                  # every rank's GPU legs are done
-    result["host_pinned"] = host_pinned_peak(dist, world)
+    if args.full or args.check_launch:
+        result["host_pinned"] = host_pinned_peak(dist, world)
     if pending is not None:
         cb = cpu_baseline(args, *pending)
         if world > 1:
@@ -1791,7 +1933,8 @@ def main():
 
     if args.workload == "c4":
         result = run_c4(args, torch, R, S, SH, L, dist, rank, world, local_rank,
-                        args.records or DEFAULT_RECORDS["c4"], mode, args.steps, args.warmup)
+                        args.records or DEFAULT_RECORDS["c4"], mode, args.steps, args.warmup,
+                        dump_dir=args.dump_outputs)
         result["vs_baseline"] = None
         ok = result.get("validated", False)
     else:
@@ -1800,7 +1943,7 @@ def main():
         if args.workload == "c1" and not args.iov and args.iov_leg == "on":
             import copy
             la = copy.copy(args)
-            la.iov, la.no_cpu_baseline = True, True
+            la.iov, la.no_cpu_baseline, la.dump_outputs = True, True, None
             leg = run_main(la, torch, R, S, SH, L, dist, rank, world, local_rank, mode)
             ok = ok and leg["validated"]
             result["vectored_encode"] = {k: leg[k] for k in ("value", "unit", "ms_per_step", "validated", "data",

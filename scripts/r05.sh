@@ -3,40 +3,41 @@
 # per-experiment launchers of rounds 3-4; those are in the history):
 #   tests [FILES]  the GPU suite (or the given test files), -x, thread timeouts
 #   smoke          __graft_entry__.smoke()
-#   line WL [ARGS] one bench line, gpurun_out/b_<WL><TAG>.log (TAG env)
-#   default        the driver's bench command (python bench.py)
+#   line WL [ARGS] one bench line with every leg (--full), $OUT/b_<WL><TAG>.log (TAG env)
+#   default        the bench with every leg (python bench.py --full)
 #   stats [ARGS]   rocprofv3 --kernel-trace --stats of a short headline run
 # Every GPU step runs under its own timeout; the script stops at the first failure.
+# Logs and profiles go to $OUT (defaults to ./bench_out).
 set -u
-mkdir -p gpurun_out
+OUT=${OUT:-$PWD/bench_out}
+mkdir -p $OUT
 export TMPDIR=/tmp
 step=${1:-tests}; shift || true
 case $step in
   tests)
     files=${*:-tests}
     timeout -k 10 900 python -u -m pytest $files -m gpu -x -v --timeout 200 --timeout-method thread \
-      > gpurun_out/tests.log 2>&1; rc=$?
-    grep -E "passed|failed|error" gpurun_out/tests.log | tail -3; exit $rc ;;
+      > $OUT/tests.log 2>&1; rc=$?
+    grep -E "passed|failed|error" $OUT/tests.log | tail -3; exit $rc ;;
   smoke)
-    timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1; rc=$?
-    cat gpurun_out/smoke.log | tail -3; exit $rc ;;
+    timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; rc=$?
+    cat $OUT/smoke.log | tail -3; exit $rc ;;
   line)
     wl=$1; shift
-    log=gpurun_out/b_${wl}${TAG:-}.log
-    timeout -k 10 600 python -u bench.py --workload $wl --c4-leg off "$@" > $log 2>&1; rc=$?
+    log=$OUT/b_${wl}${TAG:-}.log
+    timeout -k 10 600 python -u bench.py --full --workload $wl --c4-leg off "$@" > $log 2>&1; rc=$?
     python3 scripts/summ.py $log || true; exit $rc ;;
   default)
-    timeout -k 10 900 python -u bench.py > gpurun_out/b_default.log 2>&1; rc=$?
-    python3 scripts/summ.py gpurun_out/b_default.log || true; exit $rc ;;
+    timeout -k 10 900 python -u bench.py --full > $OUT/b_default.log 2>&1; rc=$?
+    python3 scripts/summ.py $OUT/b_default.log || true; exit $rc ;;
   stats)
-    timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/stats -o run --output-format csv -- \
+    timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- \
       python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pcie --iov-leg off --cache-leg off "$@" \
-      > gpurun_out/stats.log 2>&1; rc=$?
-    find gpurun_out/stats -name "*kernel_stats.csv" | head -3; exit $rc ;;
+      > $OUT/stats.log 2>&1; rc=$?
+    find $OUT/stats -name "*kernel_stats.csv" | head -3; exit $rc ;;
   sq)
-    # SQ instruction / wait counters, two --pmc passes (kernel trace only) -> gpurun_out/sq_<WL>.json
+    # SQ instruction / wait counters, two --pmc passes (kernel trace only) -> $OUT/sq_<WL>.json
     wl=$1; shift
-    OUT=$PWD/gpurun_out
     P1="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_BRANCH SQ_WAVE_CYCLES SQ_WAIT_ANY"
     P2="SQ_WAVES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_BUSY_CYCLES SQ_INSTS_SMEM SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS"
     i=0
@@ -52,15 +53,14 @@ case $step in
   round|benches|profs)
     # the round's evidence: default line, every workload (benches), rocprof stats of c1 and c4,
     # FETCH/WRITE traffic (profs); round = both
-    OUT=$PWD/gpurun_out
     if [ $step != profs ]; then
-    timeout -k 10 600 python -u bench.py > $OUT/bench_default.log 2>&1; rc=$?; echo "bench default rc=$rc"; [ $rc -eq 0 ] || exit $rc
+    timeout -k 10 600 python -u bench.py --full > $OUT/bench_default.log 2>&1; rc=$?; echo "bench default rc=$rc"; [ $rc -eq 0 ] || exit $rc
     for wl in c2 c3 c0 c4; do
-      timeout -k 10 600 python -u bench.py --workload $wl --c4-leg off > $OUT/bench_$wl.log 2>&1; rc=$?; echo "bench $wl rc=$rc"; [ $rc -eq 0 ] || exit $rc
+      timeout -k 10 600 python -u bench.py --full --workload $wl --c4-leg off > $OUT/bench_$wl.log 2>&1; rc=$?; echo "bench $wl rc=$rc"; [ $rc -eq 0 ] || exit $rc
     done
-    timeout -k 10 400 python -u bench.py --workload c2 --frame --c4-leg off > $OUT/bench_c2f.log 2>&1; rc=$?; echo "bench c2f rc=$rc"; [ $rc -eq 0 ] || exit $rc
+    timeout -k 10 400 python -u bench.py --full --workload c2 --frame --c4-leg off > $OUT/bench_c2f.log 2>&1; rc=$?; echo "bench c2f rc=$rc"; [ $rc -eq 0 ] || exit $rc
     for wl in c1 c3 c0; do
-      timeout -k 10 400 python -u bench.py --workload $wl --iov --c4-leg off > $OUT/bench_iov_$wl.log 2>&1; rc=$?; echo "bench iov $wl rc=$rc"; [ $rc -eq 0 ] || exit $rc
+      timeout -k 10 400 python -u bench.py --full --workload $wl --iov --c4-leg off > $OUT/bench_iov_$wl.log 2>&1; rc=$?; echo "bench iov $wl rc=$rc"; [ $rc -eq 0 ] || exit $rc
     done
     fi
     [ $step = benches ] && exit 0

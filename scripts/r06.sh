@@ -38,7 +38,7 @@ case $step in
     (while sleep 45; do date +%T >> gpurun_out/heartbeat_8rank.log; done) & hb=$!
     s0=$(date +%s)
     ONC_BENCH_SAME_DEVICE=1 timeout -k 10 1000 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-      --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 8 --backend gloo \
+      --master-addr 127.0.0.1 --master-port 29531 bench.py --full --gpus 8 --backend gloo \
       > gpurun_out/bench_8ranks_same_device.log 2>&1; r=$?
     kill $hb 2>/dev/null
     echo "8 ranks rc=$r wall_s=$(( $(date +%s) - s0 ))" | tee -a gpurun_out/bench_8ranks_same_device.log; exit $r ;;

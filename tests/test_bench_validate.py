@@ -168,6 +168,64 @@ def test_decode_granules(oracle, line):
     assert got.min() >= 1 and got.max() <= 10
 
 
+def test_dump_outputs_sampled_defined_and_reproducible(oracle, tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs) on host tensors holding the
+    oracle's encode + decode of a batch: float32 / float64 files, the larger
+    arrays sampled at seeded records / byte positions that index the true
+    outputs, AUTH_UNIX parameters resolved per record (garbage in the
+    unreferenced slots and in the aux words of OK records does not show),
+    and a second dump of the same outputs writes the same files."""
+    import types
+
+    import torch
+
+    import onc_rpc_amd.layout as L
+    bm = _bench()
+    monkeypatch.setattr(bm, "DUMP_RECORDS", 1000)
+    monkeypatch.setattr(bm, "DUMP_WIRE_BYTES", 4096)
+    hb = S.mixed(3000, seed=31, pmin=0, pmax=200)
+    wire, off, st, _ = oracle.encode_batch(hb)
+    n, total = hb.n, len(wire)
+    w = np.frombuffer(bytes(wire) + b"\0" * 16, np.uint8).copy()
+    om, ou, os_, oa0, oa1 = oracle.decode_batch(w, off, L.DECODE_SLICE)
+    assert not os_.any()
+    cred, verf = L.unix_used(om, os_)
+    assert cred.any()
+
+    def outputs(junk):
+        unix = ou.copy().view(np.uint8).reshape(-1, 96)
+        used = np.zeros(2 * n, bool)
+        used[om["cred_ref"][cred].astype(np.int64)] = True
+        used[om["verf_ref"][verf].astype(np.int64)] = True
+        unix[~used] = junk
+        dec = types.SimpleNamespace(
+            msgs=torch.from_numpy(om.copy().view(np.uint8).reshape(-1)), unix=torch.from_numpy(unix.reshape(-1)),
+            status=torch.from_numpy(os_.copy()), aux0=torch.full((n,), junk, dtype=torch.int32),
+            aux1=torch.full((n,), junk, dtype=torch.int32))
+        return dict(wire=torch.from_numpy(w), wire_bytes=total, rec_off=torch.from_numpy(off.astype(np.int64)),
+                    enc_status=torch.from_numpy(st.astype(np.int32)), dec=dec)
+
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d, junk in zip(dirs, (0x11, 0x77)):
+        bm.dump_outputs(str(d), torch, L, 0, n, **outputs(junk))
+    files = sorted(p.name for p in dirs[0].iterdir())
+    assert files == sorted(p.name for p in dirs[1].iterdir()) and "wire.npy" in files
+    a = {f[:-4]: np.load(dirs[0] / f) for f in files}
+    for f in files:
+        assert a[f[:-4]].dtype in (np.float32, np.float64)
+        assert np.array_equal(a[f[:-4]], np.load(dirs[1] / f)), f
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    idx = a["sample_records"].astype(np.int64)
+    assert len(idx) == 1000 and len(set(idx.tolist())) == 1000 and idx.max() < n
+    pos = a["wire_sample_positions"].astype(np.int64)
+    assert len(pos) == 4096 and np.array_equal(a["wire"], w[pos])
+    assert np.array_equal(a["rec_off"], off[idx].astype(np.float64)) and a["rec_off_end"][0] == total
+    rm, rp = L.resolve_unix(om, ou, os_)
+    assert np.array_equal(a["dec_msgs"], rm.view(np.uint8).reshape(n, 64)[idx])
+    assert np.array_equal(a["dec_unix_params"], rp.reshape(n, -1)[idx])
+    assert not a["dec_status"].any() and not a["dec_aux0"].any() and not a["enc_status"].any()
+
+
 def test_reduce_leg_and_best():
     """bench.reduce_leg (the over-ranks reduction of the PCIe-inclusive legs,
     here on one rank): values recomputed from ms, a failed or missing

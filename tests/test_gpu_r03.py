@@ -170,7 +170,7 @@ def test_bench_two_ranks_line_has_cpu_baseline():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["ONC_BENCH_SAME_DEVICE"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo",
                         "--records", "20000", "--c4-leg", "off", "--iov-leg", "off", "--steps", "3", "--warmup", "1",
                         "--cpu-seconds", "1", "--cpu-threads", "2", "--no-pcie"],
                        env=env, cwd=root, capture_output=True, text=True, timeout=240)
