@@ -565,13 +565,14 @@ __device__ __forceinline__ void load_round1(uint32_t* s_win, int t, uintptr_t wi
     constexpr uint32_t G = kLine ? kWin1L : kWin1;
     static_assert(kWin1 == 4 && kWin1L == 8, "pin lists below");
     static_assert(kDecTile == 64, "one wave per workgroup: the hand-over needs no workgroup barrier");
+    static_assert(kWinWords * kDecTile >= 4 * 64 * G, "the cooperative hand-over (64 * G granules) fits the window");
 #pragma unroll
     for (uint32_t j = 0; j < kWin1L; ++j) v[j] = u32x4{0u, 0u, 0u, 0u};
     const uint64_t act = __ballot(nch != 0);
     if (act == 0) return;
     const int first = __builtin_ctzll(act);
-    const uintptr_t rb = uintptr_t(__builtin_amdgcn_readlane(uint32_t(win), first)) |
-                         (uintptr_t(__builtin_amdgcn_readlane(uint32_t(win >> 32), first)) << 32);
+    // (lane_u64 zero-extends each half; a bare readlane is a signed int)
+    const uintptr_t rb = lane_u64(win, first);
     const bool near = nch == 0 || (win >= rb && win - rb < (uintptr_t(1) << 31) - 256);
     const uint32_t wo = uint32_t(win - rb);
     if (__ballot(!near) == 0) {
@@ -713,8 +714,7 @@ __device__ __forceinline__ void load_round2_coop(uint32_t* s_win, int t, uintptr
     const uint64_t act = __ballot(r2);
     if (act == 0) return;
     const int first = __builtin_ctzll(act);
-    const uintptr_t rb = uintptr_t(__builtin_amdgcn_readlane(uint32_t(win), first)) |
-                         (uintptr_t(__builtin_amdgcn_readlane(uint32_t(win >> 32), first)) << 32);
+    const uintptr_t rb = lane_u64(win, first);
     const bool near = !r2 || (win >= rb && win - rb < (uintptr_t(1) << 31) - 256);
     if (__ballot(!near) != 0) {                        // windows too far apart: per-lane loads
 #pragma unroll
