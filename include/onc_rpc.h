@@ -70,7 +70,10 @@ extern "C" {
  *    timing id ONC_K_COMPACT; onc_host_unregister takes a NULL codec and
  *    registrations are counted per range (a pinned range belongs to the
  *    process); the rejected-experiment variant bits (EMIT_PRELOAD,
- *    DEC_AUX_SPARSE, SINGLE_PASS, SP_*) are gone. */
+ *    DEC_AUX_SPARSE, SINGLE_PASS, SP_*) are gone.
+ *    Added without a version change (nothing existing moved; a caller finds
+ *    them by linking): onc_decode_bounded, onc_decode_lengths_bounded,
+ *    onc_decode_body_bounded and the status ONC_DEC_BAD_EXTENT. */
 #define ONC_RPC_ABI_VERSION 8
 
 /* ------------------------------------------------------------------------ */
@@ -205,6 +208,12 @@ extern "C" {
 #define ONC_ENC_GIDS_GT_16      103 /* panic: Gids::from_iter unix_params.rs:47 */
 #define ONC_ENC_BAD_DESCRIPTOR  104 /* a descriptor the Rust enums cannot represent */
 #define ONC_ENC_WRITE_ZERO      105 /* io::Error WriteZero: output capacity exhausted */
+/* Bounded-decode-only code (onc_decode_bounded and its siblings). */
+#define ONC_DEC_BAD_EXTENT      106 /* panic: slice index out of range: the caller's
+                                       `&wire[off..off + len]`. aux0 = why (ONC_EXTENT_*), aux1 = 0 */
+#define ONC_EXTENT_START_PAST_WIRE 1 /* the record starts past wire_len */
+#define ONC_EXTENT_END_PAST_WIRE   2 /* the record ends past wire_len */
+#define ONC_EXTENT_NOT_MONOTONIC   3 /* rec_off[i+1] < rec_off[i] (offset forms) */
 
 /* Batch-level return codes of the API functions */
 #define ONC_RC_OK        0
@@ -671,6 +680,38 @@ int onc_decode_lengths(onc_codec* codec, const uint8_t* wire, const uint32_t* re
  * Same over-read rule as onc_decode. */
 int onc_decode_body(onc_codec* codec, int root, const uint8_t* wire, const uint64_t* rec_off, uint64_t n,
                     int mode, const uint32_t* param, const onc_decoded* out, uint32_t* consumed);
+
+/* ------------------------------------------------------------------------ */
+/* Bounded decode — the three decodes above with the wire's length           */
+/* ------------------------------------------------------------------------ */
+
+/* onc_decode, onc_decode_lengths and onc_decode_body trust the caller's
+ * extents; these take wire_len, the number of readable bytes from `wire`,
+ * and never read outside [wire, wire + wire_len) beyond the over-read rule
+ * of onc_decode (whole 16-byte granules that hold bytes of a record with a
+ * good extent). Offsets are relative to `wire`; `base` counts. Use them for
+ * offsets or lengths that do not come from onc_frame_stream (the reference
+ * takes a slice: RpcMessage::try_from reads only inside it,
+ * rpc_message.rs:243-267, and cutting &wire[off..off + len] out of range
+ * panics).
+ * A record whose extent lies inside the wire — an empty record at
+ * off == wire_len included — decodes exactly as by the unbounded call. A
+ * record with a bad extent gets ONC_DEC_BAD_EXTENT with aux0 = the first of
+ * ONC_EXTENT_NOT_MONOTONIC (offset forms), ONC_EXTENT_START_PAST_WIRE,
+ * ONC_EXTENT_END_PAST_WIRE that applies and aux1 = 0, a zeroed descriptor, no
+ * AUTH_UNIX slot and consumed = 0; no byte is read for it, and like any
+ * other failed record it takes no slot from its group's OK records.
+ * onc_decode_lengths_bounded still writes the true prefix sums to rec_off
+ * for every record; once they pass wire_len every later record is
+ * ONC_EXTENT_START_PAST_WIRE. Arguments, return codes, scratch
+ * (onc_codec_reserve) and graph capture are those of the unbounded calls. */
+int onc_decode_bounded(onc_codec* codec, const uint8_t* wire, uint64_t wire_len, const uint64_t* rec_off,
+                       uint64_t n, int mode, const onc_decoded* out);
+int onc_decode_lengths_bounded(onc_codec* codec, const uint8_t* wire, uint64_t wire_len, const uint32_t* rec_len,
+                               uint64_t n, uint64_t base, int mode, uint64_t* rec_off, const onc_decoded* out);
+int onc_decode_body_bounded(onc_codec* codec, int root, const uint8_t* wire, uint64_t wire_len,
+                            const uint64_t* rec_off, uint64_t n, int mode, const uint32_t* param,
+                            const onc_decoded* out, uint32_t* consumed);
 
 /* serialised_len() of every descriptor as `root` + the checks of that
  * root's serialise_into: shape (ONC_ENC_BAD_DESCRIPTOR), construction panics

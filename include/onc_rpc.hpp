@@ -29,7 +29,8 @@
 //   BatchEncoder  — the caller's serialise_into loop over many messages,
 //                   one onc_encode_body call (one pass, no length pass).
 //   BatchDecoder  — the caller's try_from loop over many records, one
-//                   onc_decode_lengths call.
+//                   onc_decode_lengths_bounded call (a record length that
+//                   runs past the wire is Error(ONC_DEC_BAD_EXTENT), unread).
 //   Both stage their inputs and outputs in the codec's mapped pinned host
 //   memory (Codec::stage): the kernels read and write it in place over PCIe
 //   — no device allocation and no copy calls, one synchronisation per call.
@@ -113,6 +114,11 @@ public:
             case ONC_ERR_INVALID_RPC_VERSION: return "invalid rpc version " + std::to_string(a0);
             case ONC_ERR_INVALID_MACHINE_NAME: return "invalid machine name";
             case ONC_ERR_IO_UNEXPECTED_EOF: return "i/o error (UnexpectedEof): failed to fill whole buffer";
+            // not a reference error: where the caller's &wire[off..off + len] would panic
+            case ONC_DEC_BAD_EXTENT:
+                return std::string("slice index out of range: record ") +
+                       (a0 == ONC_EXTENT_NOT_MONOTONIC ? "offsets decrease"
+                        : a0 == ONC_EXTENT_START_PAST_WIRE ? "starts past the wire" : "ends past the wire");
             default: {
                 const char* s = onc_status_str(code);
                 return s ? std::string(s) : "error " + std::to_string(code);
@@ -1103,7 +1109,10 @@ inline std::vector<Decoded> BatchDecoder::lengths_at(Codec& codec, const uint8_t
     std::memcpy(l.host, rec_len.data(), n * 4);
     const Out o = take_out(c, n);
     const onc_decoded d = o.dev();
-    codec.check(onc_decode_lengths(codec.get(), wd, l.dev, n, 0, int(mode), nullptr, &d), "onc_decode_lengths");
+    // bounded: the lengths are the caller's, wire_len is what was staged or
+    // registered — a record running past it is Error(ONC_DEC_BAD_EXTENT), unread
+    codec.check(onc_decode_lengths_bounded(codec.get(), wd, wire_len, l.dev, n, 0, int(mode), nullptr, &d),
+                "onc_decode_lengths_bounded");
     codec.sync();
     return results(o, n, wire);
 }

@@ -439,6 +439,7 @@ const char* onc_status_str(int32_t s) {
         case ONC_ENC_GIDS_GT_16: return "more than 16 gids";
         case ONC_ENC_BAD_DESCRIPTOR: return "invalid message descriptor";
         case ONC_ENC_WRITE_ZERO: return "failed to write whole buffer";
+        case ONC_DEC_BAD_EXTENT: return "slice index out of range: record extent outside the wire";
         default: return "unknown status";
     }
 }
@@ -901,8 +902,10 @@ int onc_frame_stream(onc_codec* c, const uint8_t* wire, uint64_t len, uint64_t* 
     return run(c, ONC_K_FRAME_WRITE, "frame_write", [&] { return onc::launch_frame_write(a, c->stream); });
 }
 
-int onc_decode(onc_codec* c, const uint8_t* wire, const uint64_t* rec_off, uint64_t n, int mode,
-               const onc_decoded* out) {
+// The decode entry points and their bounded forms share one body each:
+// bounded = the wire-length checked kernels (decode.hip kBound, extent.h).
+static int decode_offsets(onc_codec* c, const uint8_t* wire, bool bounded, uint64_t wire_len, const uint64_t* rec_off,
+                          uint64_t n, int mode, const onc_decoded* out) {
     if (!c || !out || (mode != ONC_DECODE_SLICE && mode != ONC_DECODE_BYTES)) return ONC_RC_EINVAL;
     if (n == 0) return ONC_RC_OK;
     if (!rec_off || !out->msgs || !out->unix_params || !out->status || !out->aux0 || !out->aux1)
@@ -914,12 +917,24 @@ int onc_decode(onc_codec* c, const uint8_t* wire, const uint64_t* rec_off, uint6
     a.rec_off = rec_off;
     a.out = *out;
     a.variant = c->variant;
+    a.bounded = bounded;
+    a.wire_len = wire_len;
     decode_policy(c, a);
     return run(c, ONC_K_DEC_PARSE, "decode", [&] { return onc::launch_decode(a, mode, c->stream); });
 }
 
-int onc_decode_lengths(onc_codec* c, const uint8_t* wire, const uint32_t* rec_len, uint64_t n, uint64_t base,
-                       int mode, uint64_t* rec_off, const onc_decoded* out) {
+int onc_decode(onc_codec* c, const uint8_t* wire, const uint64_t* rec_off, uint64_t n, int mode,
+               const onc_decoded* out) {
+    return decode_offsets(c, wire, false, 0, rec_off, n, mode, out);
+}
+
+int onc_decode_bounded(onc_codec* c, const uint8_t* wire, uint64_t wire_len, const uint64_t* rec_off, uint64_t n,
+                       int mode, const onc_decoded* out) {
+    return decode_offsets(c, wire, true, wire_len, rec_off, n, mode, out);
+}
+
+static int decode_lengths(onc_codec* c, const uint8_t* wire, bool bounded, uint64_t wire_len, const uint32_t* rec_len,
+                          uint64_t n, uint64_t base, int mode, uint64_t* rec_off, const onc_decoded* out) {
     if (!c || !out || (mode != ONC_DECODE_SLICE && mode != ONC_DECODE_BYTES)) return ONC_RC_EINVAL;
     if (n == 0) return ONC_RC_OK;
     if (!rec_len || !out->msgs || !out->unix_params || !out->status || !out->aux0 || !out->aux1)
@@ -944,6 +959,8 @@ int onc_decode_lengths(onc_codec* c, const uint8_t* wire, const uint32_t* rec_le
     a.nblk = nblk;
     a.base = base;
     a.rec_off_out = rec_off;
+    a.bounded = bounded;
+    a.wire_len = wire_len;
     uint64_t* blk_sum = c->scratch + 3 * T;
     // one decode workgroup (n <= 64): its offsets are its own wave scan of
     // the lengths from `base` — the totals of earlier workgroups and blocks
@@ -963,6 +980,16 @@ int onc_decode_lengths(onc_codec* c, const uint8_t* wire, const uint32_t* rec_le
         a.blk_base = blk_base;
     }
     return run(c, ONC_K_DEC_PARSE, "decode", [&] { return onc::launch_decode(a, mode, c->stream); });
+}
+
+int onc_decode_lengths(onc_codec* c, const uint8_t* wire, const uint32_t* rec_len, uint64_t n, uint64_t base,
+                       int mode, uint64_t* rec_off, const onc_decoded* out) {
+    return decode_lengths(c, wire, false, 0, rec_len, n, base, mode, rec_off, out);
+}
+
+int onc_decode_lengths_bounded(onc_codec* c, const uint8_t* wire, uint64_t wire_len, const uint32_t* rec_len,
+                               uint64_t n, uint64_t base, int mode, uint64_t* rec_off, const onc_decoded* out) {
+    return decode_lengths(c, wire, true, wire_len, rec_len, n, base, mode, rec_off, out);
 }
 
 int onc_scan_lengths(onc_codec* c, const uint32_t* rec_len, uint64_t n, uint64_t base, uint64_t* rec_off) {
@@ -995,8 +1022,9 @@ int onc_scan_lengths(onc_codec* c, const uint32_t* rec_len, uint64_t n, uint64_t
                [&] { return onc::launch_len_apply(rec_len, n, tile_base, rec_off, c->stream); });
 }
 
-int onc_decode_body(onc_codec* c, int root, const uint8_t* wire, const uint64_t* rec_off, uint64_t n, int mode,
-                    const uint32_t* param, const onc_decoded* out, uint32_t* consumed) {
+static int decode_body(onc_codec* c, int root, const uint8_t* wire, bool bounded, uint64_t wire_len,
+                       const uint64_t* rec_off, uint64_t n, int mode, const uint32_t* param, const onc_decoded* out,
+                       uint32_t* consumed) {
     if (!c || !out || (mode != ONC_DECODE_SLICE && mode != ONC_DECODE_BYTES)) return ONC_RC_EINVAL;
     if (root < 0 || root >= ONC_ROOT_COUNT) return ONC_RC_EINVAL;
     if (n == 0) return ONC_RC_OK;
@@ -1016,7 +1044,19 @@ int onc_decode_body(onc_codec* c, int root, const uint8_t* wire, const uint64_t*
     a.param = param;
     a.consumed = consumed;
     a.body = 1;
+    a.bounded = bounded;
+    a.wire_len = wire_len;
     return run(c, ONC_K_DEC_PARSE, "decode", [&] { return onc::launch_decode(a, mode, c->stream); });
+}
+
+int onc_decode_body(onc_codec* c, int root, const uint8_t* wire, const uint64_t* rec_off, uint64_t n, int mode,
+                    const uint32_t* param, const onc_decoded* out, uint32_t* consumed) {
+    return decode_body(c, root, wire, false, 0, rec_off, n, mode, param, out, consumed);
+}
+
+int onc_decode_body_bounded(onc_codec* c, int root, const uint8_t* wire, uint64_t wire_len, const uint64_t* rec_off,
+                            uint64_t n, int mode, const uint32_t* param, const onc_decoded* out, uint32_t* consumed) {
+    return decode_body(c, root, wire, true, wire_len, rec_off, n, mode, param, out, consumed);
 }
 
 int onc_encode_body_lengths(onc_codec* c, int root, const onc_batch* batch, uint32_t* rec_len, int32_t* status) {

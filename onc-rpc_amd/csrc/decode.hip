@@ -15,6 +15,7 @@
 // the reference does (short reads: IOError vs InvalidLength; AUTH_UNIX is
 // parsed inside its length-bounded slice in Bytes mode).
 #include "common.h"
+#include "extent.h"
 #include "kernels.h"
 
 namespace onc {
@@ -807,7 +808,7 @@ __device__ __forceinline__ uint32_t stage_round2(uint32_t* s_win, int t, uintptr
 }
 
 template <int MODE, bool kExact = false, bool kNTOut = false, bool kFromLen = false, bool kBlkFused = false,
-          bool kRoot = false, bool kLine = false>
+          bool kRoot = false, bool kLine = false, bool kBound = false>
 __global__ __launch_bounds__(kDecTile) void decode_kernel(DecArgs a) {
     __shared__ uint32_t s_win[kWinWords * kDecTile];
     static_assert(kWinWords * kDecTile * 4 >= kDecTile * sizeof(onc_msg), "descriptor staging reuses the window");
@@ -862,6 +863,19 @@ __global__ __launch_bounds__(kDecTile) void decode_kernel(DecArgs a) {
         b = a.rec_off[i];
         L = a.rec_off[i + 1] - b;
     }
+    // kBound (onc_decode*_bounded): a record whose extent leaves the wire
+    // (the reference's &wire[off..off + len] panics) is presented to the
+    // loaders as an empty record at offset 0 — no chunk in either round, no
+    // part in the choice of the wave's buffer base (load_round1 and
+    // load_round2_coop look only at lanes with chunks to load) — and takes
+    // its status below without being parsed: no load is issued for it.
+    // (Offsets form: b + L is rec_off[i + 1] again, modulo 2^64.)
+    uint32_t bad = kExtentOk;
+    if constexpr (kBound) {
+        if (valid)
+            bad = kFromLen ? extent_reason_len(a.base, b, L, a.wire_len) : extent_reason_off(b, b + L, a.wire_len);
+        if (bad != kExtentOk) b = L = 0;
+    }
     const uintptr_t wire = reinterpret_cast<uintptr_t>(a.wire);
     const uintptr_t base = wire + b;
     const uintptr_t win = base & ~uintptr_t(15);
@@ -901,7 +915,10 @@ __global__ __launch_bounds__(kDecTile) void decode_kernel(DecArgs a) {
     us.mask = 0;
     uint32_t consumed = 0;
     if (valid) {
-        if constexpr (kRoot) {
+        if (kBound && bad != kExtentOk) {
+            st = ONC_DEC_BAD_EXTENT;
+            aux0 = bad;
+        } else if constexpr (kRoot) {
             // records of 4 GiB or more: their payload does not fit the
             // descriptor's 32-bit length
             if (a.root == ONC_ROOT_RPC_MESSAGE) {
@@ -1028,43 +1045,49 @@ hipError_t launch_dlen_tiles(const uint32_t* rec_len, uint64_t n, uint64_t* tile
     return hipGetLastError();
 }
 
-// The message decode (onc_decode / onc_decode_lengths) under one first-round
-// policy (kLine, decode_kernel).
-template <bool kLine>
+// The message decode (onc_decode / onc_decode_lengths and their bounded
+// forms, kBound) under one first-round policy (kLine, decode_kernel).
+template <bool kLine, bool kBound>
 hipError_t launch_message_decode(const DecArgs& a, int mode, hipStream_t s) {
     const uint64_t wgs = (a.n + kDecTile - 1) / kDecTile;
     const dim3 g{uint32_t(wgs)}, b{uint32_t(kDecTile)};
     if (a.rec_len) {
         const bool fused = a.blk_base == nullptr;
         if (mode == ONC_DECODE_BYTES) {
-            if (fused) ONC_LAUNCH((decode_kernel<ONC_DECODE_BYTES, true, true, true, true, false, kLine>), g, b, 0, s, a);
-            else ONC_LAUNCH((decode_kernel<ONC_DECODE_BYTES, true, true, true, false, false, kLine>), g, b, 0, s, a);
+            if (fused) ONC_LAUNCH((decode_kernel<ONC_DECODE_BYTES, true, true, true, true, false, kLine, kBound>), g, b, 0, s, a);
+            else ONC_LAUNCH((decode_kernel<ONC_DECODE_BYTES, true, true, true, false, false, kLine, kBound>), g, b, 0, s, a);
         } else {
-            if (fused) ONC_LAUNCH((decode_kernel<ONC_DECODE_SLICE, true, true, true, true, false, kLine>), g, b, 0, s, a);
-            else ONC_LAUNCH((decode_kernel<ONC_DECODE_SLICE, true, true, true, false, false, kLine>), g, b, 0, s, a);
+            if (fused) ONC_LAUNCH((decode_kernel<ONC_DECODE_SLICE, true, true, true, true, false, kLine, kBound>), g, b, 0, s, a);
+            else ONC_LAUNCH((decode_kernel<ONC_DECODE_SLICE, true, true, true, false, false, kLine, kBound>), g, b, 0, s, a);
         }
         return hipGetLastError();
     }
     if (mode == ONC_DECODE_BYTES)
-        ONC_LAUNCH((decode_kernel<ONC_DECODE_BYTES, true, true, false, false, false, kLine>), g, b, 0, s, a);
+        ONC_LAUNCH((decode_kernel<ONC_DECODE_BYTES, true, true, false, false, false, kLine, kBound>), g, b, 0, s, a);
     else
-        ONC_LAUNCH((decode_kernel<ONC_DECODE_SLICE, true, true, false, false, false, kLine>), g, b, 0, s, a);
+        ONC_LAUNCH((decode_kernel<ONC_DECODE_SLICE, true, true, false, false, false, kLine, kBound>), g, b, 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_decode(const DecArgs& a, int mode, hipStream_t s) {
+template <bool kBound>
+hipError_t launch_decode_any(const DecArgs& a, int mode, hipStream_t s) {
     if (a.body) {
         const uint64_t tiles = (a.n + kDecTile - 1) / kDecTile;
         if (mode == ONC_DECODE_BYTES)
-            ONC_LAUNCH((decode_kernel<ONC_DECODE_BYTES, true, true, false, false, true>), dim3(uint32_t(tiles)),
-                       dim3(kDecTile), 0, s, a);
+            ONC_LAUNCH((decode_kernel<ONC_DECODE_BYTES, true, true, false, false, true, false, kBound>),
+                       dim3(uint32_t(tiles)), dim3(kDecTile), 0, s, a);
         else
-            ONC_LAUNCH((decode_kernel<ONC_DECODE_SLICE, true, true, false, false, true>), dim3(uint32_t(tiles)),
-                       dim3(kDecTile), 0, s, a);
+            ONC_LAUNCH((decode_kernel<ONC_DECODE_SLICE, true, true, false, false, true, false, kBound>),
+                       dim3(uint32_t(tiles)), dim3(kDecTile), 0, s, a);
         return hipGetLastError();
     }
-    if (a.line) return launch_message_decode<true>(a, mode, s);
-    return launch_message_decode<false>(a, mode, s);
+    if (a.line) return launch_message_decode<true, kBound>(a, mode, s);
+    return launch_message_decode<false, kBound>(a, mode, s);
+}
+
+hipError_t launch_decode(const DecArgs& a, int mode, hipStream_t s) {
+    if (a.bounded) return launch_decode_any<true>(a, mode, s);
+    return launch_decode_any<false>(a, mode, s);
 }
 
 }  // namespace onc

@@ -146,6 +146,9 @@ struct DecArgs {
     uint32_t* consumed;         // optional: bytes the decoded value occupies
     uint32_t* hint;             // the codec's policy word (mapped host memory; decode.hip kLine) or NULL
     uint32_t line;              // message decode: the line policy (decode.hip kLine)
+    // onc_decode*_bounded (last, so the fields above keep their kernarg offsets)
+    uint32_t bounded;           // 1: the wire-length checked kernels (decode_kernel<..., kBound>)
+    uint64_t wire_len;          // readable bytes from `wire`
 };
 // the line policy when at least this many of a sampled workgroup's 64
 // records needed a second first-round window under the standard one

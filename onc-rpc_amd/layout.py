@@ -53,7 +53,12 @@ STATUS = {
     13: "IOError(UnexpectedEof)",
     100: "EncTooLong", 101: "EncAuthGt200", 102: "EncNameGt255", 103: "EncGidsGt16",
     104: "EncBadDescriptor", 105: "EncWriteZero",
+    106: "DecBadExtent",
 }
+# bounded decode (onc_decode*_bounded): a record extent outside the wire;
+# aux0 = the reason, in the order the checks are made
+DEC_BAD_EXTENT = 106
+EXTENT_START_PAST_WIRE, EXTENT_END_PAST_WIRE, EXTENT_NOT_MONOTONIC = 1, 2, 3
 
 # --- dtypes ------------------------------------------------------------------
 MSG_DTYPE = np.dtype({

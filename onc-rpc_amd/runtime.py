@@ -37,6 +37,7 @@ EXPORTED = [
     "onc_decode_lengths", "onc_decode_body", "onc_encode_body", "onc_encode_body_lengths",
     "onc_codec_create_ex", "onc_codec_set_decode_policy", "onc_host_register", "onc_host_unregister",
     "onc_compact", "onc_compact_iov",
+    "onc_decode_bounded", "onc_decode_lengths_bounded", "onc_decode_body_bounded",
 ]
 
 # onc_codec_options (include/onc_rpc.h)
@@ -113,6 +114,9 @@ def load_library(path=LIB_PATH):
     lib.onc_host_unregister.argtypes = [vp, vp]
     lib.onc_compact.argtypes = [vp, vp, vp, vp, u64, C.POINTER(C.c_uint64)]
     lib.onc_compact_iov.argtypes = [vp, vp, vp, u64, vp]
+    lib.onc_decode_bounded.argtypes = [vp, vp, u64, vp, u64, i32, C.POINTER(OncDecoded)]
+    lib.onc_decode_lengths_bounded.argtypes = [vp, vp, u64, vp, u64, u64, i32, vp, C.POINTER(OncDecoded)]
+    lib.onc_decode_body_bounded.argtypes = [vp, i32, vp, u64, vp, u64, i32, vp, C.POINTER(OncDecoded), vp]
     for name in EXPORTED:
         getattr(lib, name).restype = getattr(lib, name).restype or i32
     # a stale library would read a differently laid out onc_batch and label
@@ -311,6 +315,30 @@ class Codec:
                        aux1.data_ptr())
         self._check(self.lib.onc_decode_body(self.h, root, _ptr(wire), _ptr(rec_off), n, mode, _ptr(param),
                                              C.byref(d), _ptr(consumed)), "onc_decode_body")
+
+    # -- bounded decode: the three above with the wire's readable length ------
+    # (a record whose extent leaves [0, wire_len) is L.DEC_BAD_EXTENT, unread)
+    def decode_bounded(self, wire, wire_len, rec_off, n, mode, msgs, unix, status, aux0, aux1):
+        d = OncDecoded(msgs.data_ptr(), unix.data_ptr(), status.data_ptr(), aux0.data_ptr(),
+                       aux1.data_ptr())
+        self._check(self.lib.onc_decode_bounded(self.h, _ptr(wire), wire_len, _ptr(rec_off), n, mode, C.byref(d)),
+                    "onc_decode_bounded")
+
+    def decode_lengths_bounded(self, wire, wire_len, rec_len, n, base, mode, msgs, unix, status, aux0, aux1,
+                               rec_off=None):
+        d = OncDecoded(msgs.data_ptr(), unix.data_ptr(), status.data_ptr(), aux0.data_ptr(),
+                       aux1.data_ptr())
+        self._check(self.lib.onc_decode_lengths_bounded(self.h, _ptr(wire), wire_len, _ptr(rec_len), n, base, mode,
+                                                        _ptr(rec_off) if rec_off is not None else None, C.byref(d)),
+                    "onc_decode_lengths_bounded")
+
+    def decode_body_bounded(self, root, wire, wire_len, rec_off, n, mode, msgs, unix, status, aux0, aux1,
+                            param=None, consumed=None):
+        d = OncDecoded(msgs.data_ptr(), unix.data_ptr(), status.data_ptr(), aux0.data_ptr(),
+                       aux1.data_ptr())
+        self._check(self.lib.onc_decode_body_bounded(self.h, root, _ptr(wire), wire_len, _ptr(rec_off), n, mode,
+                                                     _ptr(param), C.byref(d), _ptr(consumed)),
+                    "onc_decode_body_bounded")
 
     def encode_body_lengths(self, root, batch: DeviceBatch, rec_len, status):
         b = batch.c_struct()
