@@ -73,7 +73,10 @@ extern "C" {
  *    DEC_AUX_SPARSE, SINGLE_PASS, SP_*) are gone.
  *    Added without a version change (nothing existing moved; a caller finds
  *    them by linking): onc_decode_bounded, onc_decode_lengths_bounded,
- *    onc_decode_body_bounded and the status ONC_DEC_BAD_EXTENT. */
+ *    onc_decode_body_bounded and the status ONC_DEC_BAD_EXTENT;
+ *    onc_frame_fragments and onc_defragment (multi-fragment record streams)
+ *    with the timing ids ONC_K_DEFRAG_PLAN / ONC_K_DEFRAG_COPY appended
+ *    (ONC_K_COUNT 16: onc_codec_kernel_stats writes that many entries). */
 #define ONC_RPC_ABI_VERSION 8
 
 /* ------------------------------------------------------------------------ */
@@ -417,7 +420,9 @@ int onc_codec_sync(onc_codec* codec);
  * stream is capturing returns ONC_RC_ECAPTURE (outside a capture the
  * scratch grows on demand with a synchronous hipMalloc). onc_frame_stream
  * keeps its own per-chunk scratch, sized by its first call on a stream that
- * long or longer (growing it inside a capture is ONC_RC_ECAPTURE too). */
+ * long or longer (growing it inside a capture is ONC_RC_ECAPTURE too);
+ * onc_frame_fragments shares it. onc_defragment of up to max_records
+ * fragments is covered too (32 bytes of scratch per fragment). */
 int onc_codec_reserve(onc_codec* codec, uint64_t max_records);
 /* Map a caller's host buffer (a socket buffer: any malloc'd or mmap'd
  * range) for the kernels, so that an encode / decode reads and writes it in
@@ -463,7 +468,10 @@ int onc_abi_version(void);
  * (frame_cblk, or frame_counts ahead of the three-launch scan beyond 512k
  * chunks); ONC_K_FRAME_WRITE its start copy, which up to 512k chunks also
  * sums each chunk's first record index. The body-level calls use the ids of
- * the kernels they launch (ONC_K_ENC_LEN / _ENC_EMIT / _DEC_PARSE). */
+ * the kernels they launch (ONC_K_ENC_LEN / _ENC_EMIT / _DEC_PARSE).
+ * onc_frame_fragments launches at onc_frame_stream's sites (ONC_K_FRAME_*);
+ * ONC_K_DEFRAG_PLAN is every planning launch of onc_defragment (its length
+ * scan counts as onc_scan_lengths'), ONC_K_DEFRAG_COPY the byte copy. */
 #define ONC_K_ENC_LEN      0
 #define ONC_K_SCAN_TILES   1
 #define ONC_K_ENC_EMIT     2
@@ -478,7 +486,9 @@ int onc_abi_version(void);
 #define ONC_K_FRAME_COUNTS 11
 #define ONC_K_FRAME_GUESS  12
 #define ONC_K_COMPACT      13
-#define ONC_K_COUNT        14
+#define ONC_K_DEFRAG_PLAN  14
+#define ONC_K_DEFRAG_COPY  15
+#define ONC_K_COUNT        16
 #define ONC_TIMING_ALL    (-1)
 int onc_codec_enable_timing(onc_codec* codec, int enable);
 int onc_codec_kernel_stats(onc_codec* codec, double* ms_total /*[ONC_K_COUNT]*/,
@@ -644,6 +654,75 @@ int32_t onc_expected_message_len(const uint8_t* data, uint64_t len, uint32_t* ou
  * SURVEY §8(f) rank 1. */
 int onc_frame_stream(onc_codec* codec, const uint8_t* wire, uint64_t len,
                      uint64_t* rec_off, uint64_t max_records, uint64_t* result);
+
+/* onc_frame_stream at fragment level (RFC 5531 §11: a record is one or more
+ * fragments, the last one marked by bit 31 of its mark — streams the
+ * reference rejects: Error::Fragmented, rpc_message.rs:359-362, "No support
+ * for fragmented messages", README.md:62). Every mark starts a fragment,
+ * whatever its last-fragment bit; the result is that of
+ *
+ *   p = 0; n = 0; st = ONC_OK
+ *   while p < len and n < max_frags:
+ *       if len - p < 4:     st = ONC_ERR_INCOMPLETE_HEADER; break
+ *       h = be32(wire, p); want = (h & 0x7FFFFFFF) + 4        (rpc_message.rs:343-367 without :359-362)
+ *       if len - p < want:  st = ONC_ERR_INCOMPLETE_MESSAGE; aux0 = len - p; aux1 = want; break
+ *       frag_off[n++] = p; p += want
+ *   frag_off[n] = p; result = {n, p, st, aux0, aux1}
+ *
+ * so ONC_ERR_FRAGMENTED is never reported; len == 0 or max_frags == 0 gives
+ * all zeros. Arguments, scratch, ONC_RC_ECAPTURE, frame_chunk and the timing
+ * ids are onc_frame_stream's: the same speculative machine in its fragment
+ * mode (frame.hip), where a chunk's chain runs on through continuation
+ * fragments — which carry no RPC header to guess by — up to the next guess.
+ * When onc_frame_stream stops with ONC_ERR_FRAGMENTED at `consumed`, call
+ * this and onc_defragment on the rest of the buffer, then go on as usual on
+ * onc_defragment's output. */
+int onc_frame_fragments(onc_codec* codec, const uint8_t* wire, uint64_t len,
+                        uint64_t* frag_off /*[dev, max_frags + 1]*/, uint64_t max_frags,
+                        uint64_t* result /*[dev, 5]: n, consumed, status, aux0, aux1*/);
+
+/* Rebuild framed fragments as the packed stream of single-fragment records
+ * that RpcMessage::serialise_into writes (one mark with the last-fragment bit
+ * and the total length, rpc_message.rs:156, then the body), so that
+ * onc_frame_stream, onc_decode and everything after them apply unchanged.
+ * Fragment j is wire[frag_off[j], frag_off[j+1]): a 4-byte mark, read only
+ * for bit 31, and a body. The offsets are trusted, as in onc_decode (they
+ * come from onc_frame_fragments). Record r is the run of fragments ending at
+ * the r-th fragment with bit 31 set; B_r = the sum of its bodies' lengths.
+ *   rec_off[dev, nfrag + 1]: rec_off[0] = 0; a record takes 4 + B_r bytes; a
+ *                     record with B_r >= 2^31 takes none and gets
+ *                     ONC_ENC_TOO_LONG (the mark cannot say it:
+ *                     rpc_message.rs:146-151). Placement ignores out_cap, so
+ *                     rec_off[n_records] is the capacity the batch needs.
+ *   out[dev]        : an OK record is BE32(0x80000000 | B_r), then its
+ *                     fragments' bodies in order. A record that would end
+ *                     beyond out_cap gets ONC_ENC_WRITE_ZERO and none of its
+ *                     bytes are written. Any byte address (as onc_encode);
+ *                     no byte before out, at or after out + out_cap, or
+ *                     outside an OK record's extent is written. out must not
+ *                     overlap wire.
+ *   status[dev, nfrag]: per record, ONC_OK / ONC_ENC_TOO_LONG / ONC_ENC_WRITE_ZERO.
+ *   result[dev, 6]  : {n_records, wire_consumed, out_bytes, pending_frags,
+ *                     pending_body_bytes, n_multi}. Fragments after the last
+ *                     one with bit 31 set belong to no complete record: they
+ *                     are not emitted, only counted (pending_*);
+ *                     wire_consumed = frag_off[first pending fragment], or
+ *                     frag_off[nfrag]; out_bytes = rec_off[n_records];
+ *                     n_multi = records of more than one fragment.
+ * Entries of rec_off past n_records and of status from n_records on are not
+ * written. nfrag == 0 gives rec_off[0] = 0 and a zero result. Zero-length
+ * fragments are legal anywhere; an empty record is the bare mark 80 00 00 00.
+ * Wire reads follow onc_decode's rule: only whole aligned 16-byte granules
+ * that hold fragment bytes. Asynchronous on the codec's stream. Scratch: 32
+ * bytes per fragment, covered by onc_codec_reserve(max_records >= nfrag);
+ * growing it inside a capture is ONC_RC_ECAPTURE.
+ * Kernels (defrag.hip): a plan over fragments (a scan of body bytes and
+ * last-fragment bits, then onc_scan_lengths of the record lengths) and a
+ * copy partitioned by output bytes. SURVEY §8(f) rank 1. */
+int onc_defragment(onc_codec* codec, const uint8_t* wire, const uint64_t* frag_off, uint64_t nfrag,
+                   uint8_t* out, uint64_t out_cap,
+                   uint64_t* rec_off /*[dev, nfrag + 1]*/, int32_t* status /*[dev, nfrag]*/,
+                   uint64_t* result /*[dev, 6]*/);
 
 /* Exclusive scan of record lengths into offsets:
  * rec_off[0] = base, rec_off[i+1] = rec_off[i] + rec_len[i]  ([dev]). */

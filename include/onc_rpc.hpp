@@ -1168,6 +1168,71 @@ inline std::vector<Decoded> BatchDecoder::stream_at(Codec& codec, const uint8_t*
 }
 
 // ----------------------------------------------------------------------------
+// Multi-fragment record streams (RFC 5531 §11) — the reference rejects them
+// (Error::Fragmented, rpc_message.rs:359-362; README.md:62)
+// ----------------------------------------------------------------------------
+// A socket read buffer whose records may come in several fragments, rebuilt
+// on the device (onc_frame_fragments + onc_defragment) as the packed stream
+// of single-fragment records serialise_into would have written. `bytes` goes
+// to BatchDecoder::try_from_stream as it is; the decoded payload views then
+// point into `bytes`, which must outlive them.
+struct Reassembled {
+    std::vector<uint8_t> bytes;      // the reassembled stream (rec_off.back() bytes)
+    std::vector<uint64_t> rec_off;   // n + 1 offsets into bytes
+    std::vector<int32_t> status;     // per record: ONC_OK or ONC_ENC_TOO_LONG (a body of 2^31 bytes or more)
+    size_t consumed = 0;             // wire bytes of the complete records: keep the rest for the next read
+    size_t pending_frags = 0;        // framed fragments after the last complete record
+    size_t pending_body_bytes = 0;
+    size_t n_multi = 0;              // records that came in more than one fragment
+    std::optional<Error> stop;       // why fragment framing stopped before the buffer's end, if it did
+};
+
+inline Reassembled reassemble_stream(Codec& codec, const uint8_t* wire, size_t len) {
+    using detail::need;
+    Reassembled r;
+    r.rec_off.assign(1, 0);
+    const size_t max_frags = len / 4 + 1;
+    detail::Carve c{codec.stage(need<uint8_t>(len) + need<uint64_t>(max_frags + 1) + need<uint64_t>(5))};
+    const auto w = c.take<uint8_t>(len);
+    if (len) std::memcpy(w.host, wire, len);
+    const size_t frag_at = c.off;
+    const auto frag = c.take<uint64_t>(max_frags + 1);
+    const auto fres = c.take<uint64_t>(5);
+    codec.check(onc_frame_fragments(codec.get(), w.dev, len, frag.dev, max_frags, fres.dev), "onc_frame_fragments");
+    codec.sync();
+    uint64_t f[5];
+    std::memcpy(f, fres.host, sizeof(f));
+    if (int32_t(f[2]) != ONC_OK) r.stop = Error(int32_t(f[2]), uint32_t(f[3]), uint32_t(f[4]));
+    const size_t nfrag = size_t(f[0]);
+    if (!nfrag) return r;
+    // the outputs after what is staged (a stage that grows keeps it); a
+    // reassembled record is never longer than its fragments
+    const size_t mark = c.off;
+    const size_t cap = size_t(f[1]);
+    c.s = codec.stage(mark + need<uint8_t>(cap) + need<uint64_t>(nfrag + 1) + need<int32_t>(nfrag) + need<uint64_t>(6),
+                      mark);
+    const auto out = c.take<uint8_t>(cap);
+    const auto off = c.take<uint64_t>(nfrag + 1);
+    const auto st = c.take<int32_t>(nfrag);
+    const auto res = c.take<uint64_t>(6);
+    codec.check(onc_defragment(codec.get(), c.s.dev, reinterpret_cast<const uint64_t*>(c.s.dev + frag_at), nfrag,
+                               out.dev, cap, off.dev, st.dev, res.dev),
+                "onc_defragment");
+    codec.sync();
+    uint64_t d[6];
+    std::memcpy(d, res.host, sizeof(d));
+    const size_t n = size_t(d[0]);
+    r.bytes.assign(out.host, out.host + d[2]);
+    r.rec_off.assign(off.host, off.host + n + 1);
+    r.status.assign(st.host, st.host + n);
+    r.consumed = size_t(d[1]);
+    r.pending_frags = size_t(d[3]);
+    r.pending_body_bytes = size_t(d[4]);
+    r.n_multi = size_t(d[5]);
+    return r;
+}
+
+// ----------------------------------------------------------------------------
 // RpcMessage single-message forms (batches of one)
 // ----------------------------------------------------------------------------
 inline uint32_t RpcMessage::serialised_len(Codec& codec) const {

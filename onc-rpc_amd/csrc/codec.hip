@@ -52,6 +52,9 @@ struct onc_codec {
     uint64_t cmp_off_cap = 0;     // records
     uint8_t* cmp_bytes = nullptr;
     uint64_t cmp_bytes_cap = 0;
+    // onc_defragment: the per-fragment plan (kernels.h DefragArgs)
+    uint8_t* dfr = nullptr;
+    uint64_t dfr_cap = 0;         // fragments
     uint32_t timing = 0;   // bitmask of ONC_K_* ids whose launches are bracketed
     struct Pending {
         int kernel;
@@ -208,6 +211,34 @@ void bind_scratch(onc_codec* c, onc::EncArgs& a) {
     a.block_base = c->scratch + 3 * T + B;
 }
 
+// onc_defragment's scratch for up to F fragments: E (F + 1), off (F + 1),
+// S (F) as u64, M (F) as u32, the block states and two info words — 28 bytes
+// per fragment (the record lengths, 4 more, are ensure_lens').
+uint64_t defrag_blocks(uint64_t F) { return (F + 255) / 256; }
+uint64_t defrag_bytes(uint64_t F) {
+    return 8 * (F + 2) * 3 + 4 * (F + 2) + sizeof(onc::DefragAgg) * (defrag_blocks(F) + 1) + 16;
+}
+int ensure_defrag(onc_codec* c, uint64_t nfrag) {
+    if (nfrag <= c->dfr_cap) return ONC_RC_OK;
+    if (capturing(c)) return refuse_in_capture(c);
+    // the size asked for (a reserve of many records is not rounded up), or
+    // twice the last one for calls that keep growing
+    const uint64_t want = std::max<uint64_t>(std::max<uint64_t>(nfrag, 2 * c->dfr_cap), 65536);
+    if (c->dfr) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(c->dfr);
+        c->dfr = nullptr;
+        c->dfr_cap = 0;
+    }
+    const hipError_t e = hipMalloc(&c->dfr, defrag_bytes(want));
+    if (e != hipSuccess) {
+        fail(c, e, "hipMalloc(defragment scratch)");
+        return ONC_RC_ENOMEM;
+    }
+    c->dfr_cap = want;
+    return ONC_RC_OK;
+}
+
 int set_device(onc_codec* c) {
     const hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return fail(c, e, "hipSetDevice");
@@ -287,6 +318,7 @@ int onc_codec_destroy(onc_codec* c) {
     if (c->lens) (void)hipFree(c->lens);
     if (c->cmp_off) (void)hipFree(c->cmp_off);
     if (c->cmp_bytes) (void)hipFree(c->cmp_bytes);
+    if (c->dfr) (void)hipFree(c->dfr);
     if (c->dec_hint_host) (void)hipHostFree(c->dec_hint_host);
     delete c;
     return ONC_RC_OK;
@@ -319,7 +351,11 @@ int onc_codec_reserve(onc_codec* c, uint64_t max_records) {
     if (rc != ONC_RC_OK) return rc;
     // the plan's record lengths: onc_encode plans a chunk at a time, but
     // onc_encode_plan plans the whole batch at once (4 bytes per record)
-    return ensure_lens(c, max_records);
+    const int rl = ensure_lens(c, max_records);
+    if (rl != ONC_RC_OK) return rl;
+    // onc_defragment of up to max_records fragments: its plan (the scan of
+    // its record lengths, one per fragment at most, fits the scratch above)
+    return ensure_defrag(c, max_records);
 }
 
 // Host ranges onc_host_register pinned, process-wide (a pinned range belongs
@@ -460,6 +496,8 @@ const char* onc_kernel_name(int k) {
         case ONC_K_FRAME_COUNTS: return "frame_counts_kernel";
         case ONC_K_FRAME_GUESS: return "frame_guess_kernel";
         case ONC_K_COMPACT: return "compact_kernels";
+        case ONC_K_DEFRAG_PLAN: return "defrag_plan_kernels";
+        case ONC_K_DEFRAG_COPY: return "defrag_copy_kernel";
         default: return "?";
     }
 }
@@ -815,8 +853,10 @@ int onc_encode_iov(onc_codec* c, const onc_batch* batch, uint8_t* hdr_out, uint6
 // scan's tile sums.
 static size_t frame_bytes(uint64_t P) { return P * (56 + 8 * 64) + 2 * (P / 256 + 2) + 2 * (P / 65536 + 2) + (onc::num_tiles(P) + 1) * 16 + 128; }
 
-int onc_frame_stream(onc_codec* c, const uint8_t* wire, uint64_t len, uint64_t* rec_off, uint64_t max_records,
-                     uint64_t* result) {
+// onc_frame_stream (frag = false) and onc_frame_fragments share everything
+// but the instances of the guess, chase and walk kernels (frame.hip kFrag).
+static int frame_stream(onc_codec* c, const uint8_t* wire, uint64_t len, uint64_t* rec_off, uint64_t max_records,
+                        uint64_t* result, bool frag) {
     if (!c || !rec_off || !result || (len && !wire)) return ONC_RC_EINVAL;
     if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
     hipError_t e;
@@ -875,11 +915,11 @@ int onc_frame_stream(onc_codec* c, const uint8_t* wire, uint64_t len, uint64_t* 
     uint64_t* tile_base = tail + nt + 1;
     a.first_fail = tail + 2 * (nt + 1);
     a.first_stop = a.first_fail + 1;
-    int rc = run(c, ONC_K_FRAME_GUESS, "frame_guess", [&] { return onc::launch_frame_guess(a, c->stream); });
+    int rc = run(c, ONC_K_FRAME_GUESS, "frame_guess", [&] { return onc::launch_frame_guess(a, c->stream, frag); });
     if (rc != ONC_RC_OK) return rc;
-    rc = run(c, ONC_K_FRAME, "frame_chunks", [&] { return onc::launch_frame_chunks(a, c->stream); });
+    rc = run(c, ONC_K_FRAME, "frame_chunks", [&] { return onc::launch_frame_chunks(a, c->stream, frag); });
     if (rc != ONC_RC_OK) return rc;
-    rc = run(c, ONC_K_FRAME_WALK, "frame_walk", [&] { return onc::launch_frame_walk(a, c->stream); });
+    rc = run(c, ONC_K_FRAME_WALK, "frame_walk", [&] { return onc::launch_frame_walk(a, c->stream, frag); });
     if (rc != ONC_RC_OK) return rc;
     if (onc::frame_fused_scan_ok(P) && !c->force_scan) {
         // counts + block totals, then a wave per chunk summing its first
@@ -900,6 +940,16 @@ int onc_frame_stream(onc_codec* c, const uint8_t* wire, uint64_t len, uint64_t* 
              [&] { return onc::launch_len_apply(a.cnt_eff, P, tile_base, a.cnt_base, c->stream); });
     if (rc != ONC_RC_OK) return rc;
     return run(c, ONC_K_FRAME_WRITE, "frame_write", [&] { return onc::launch_frame_write(a, c->stream); });
+}
+
+int onc_frame_stream(onc_codec* c, const uint8_t* wire, uint64_t len, uint64_t* rec_off, uint64_t max_records,
+                     uint64_t* result) {
+    return frame_stream(c, wire, len, rec_off, max_records, result, false);
+}
+
+int onc_frame_fragments(onc_codec* c, const uint8_t* wire, uint64_t len, uint64_t* frag_off, uint64_t max_frags,
+                        uint64_t* result) {
+    return frame_stream(c, wire, len, frag_off, max_frags, result, true);
 }
 
 // The decode entry points and their bounded forms share one body each:
@@ -1154,6 +1204,57 @@ int onc_compact_iov(onc_codec* c, onc_iov_rec* iov, const int32_t* status, uint6
     if (rc != ONC_RC_OK) return rc;
     return run(c, ONC_K_COMPACT, "compact_iov_apply",
                [&] { return onc::launch_compact_iov_apply(iov, status, n, c->cmp_off, totals, c->stream); });
+}
+
+int onc_defragment(onc_codec* c, const uint8_t* wire, const uint64_t* frag_off, uint64_t nfrag, uint8_t* out,
+                   uint64_t out_cap, uint64_t* rec_off, int32_t* status, uint64_t* result) {
+    if (!c || !rec_off || !result) return ONC_RC_EINVAL;
+    if (nfrag && (!wire || !frag_off || !status || (!out && out_cap))) return ONC_RC_EINVAL;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    hipError_t e;
+    if (nfrag == 0) {
+        e = hipMemsetAsync(result, 0, 6 * sizeof(uint64_t), c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(rec_off, 0, sizeof(uint64_t), c->stream);
+        return e == hipSuccess ? ONC_RC_OK : fail(c, e, "hipMemsetAsync");
+    }
+    int rc = ensure_lens(c, nfrag);
+    if (rc == ONC_RC_OK) rc = ensure_scratch(c, onc::num_tiles(nfrag));
+    if (rc == ONC_RC_OK) rc = ensure_defrag(c, nfrag);
+    if (rc != ONC_RC_OK) return rc;
+    forget_plan(c);
+    const uint64_t F = c->dfr_cap;
+    onc::DefragArgs a{};
+    a.wire = wire;
+    a.frag_off = frag_off;
+    a.nfrag = nfrag;
+    const uintptr_t oa = reinterpret_cast<uintptr_t>(out);
+    a.out = reinterpret_cast<uint8_t*>(oa & ~uintptr_t(15));
+    a.origin = oa & 15;
+    a.out_cap = out_cap;
+    a.rec_off = rec_off;
+    a.status = status;
+    a.result = result;
+    a.E = reinterpret_cast<uint64_t*>(c->dfr);
+    a.off = a.E + (F + 2);
+    a.S = a.off + (F + 2);
+    a.blk = reinterpret_cast<onc::DefragAgg*>(a.S + (F + 2));
+    a.info = reinterpret_cast<uint64_t*>(a.blk + defrag_blocks(F) + 1);
+    a.M = reinterpret_cast<uint32_t*>(a.info + 2);
+    a.lens = c->lens;
+    // lengths past the last record scan as 0 (how many records there are is
+    // known on the device only)
+    e = hipMemsetAsync(c->lens, 0, nfrag * sizeof(uint32_t), c->stream);
+    if (e != hipSuccess) return fail(c, e, "hipMemsetAsync");
+    rc = run(c, ONC_K_DEFRAG_PLAN, "defrag_blk", [&] { return onc::launch_defrag_blk(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "defrag_blkscan", [&] { return onc::launch_defrag_blkscan(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "defrag_frag", [&] { return onc::launch_defrag_frag(a, c->stream); });
+    if (rc == ONC_RC_OK) rc = onc_scan_lengths(c, c->lens, nfrag, 0, a.off);
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "defrag_place", [&] { return onc::launch_defrag_place(a, c->stream); });
+    if (rc != ONC_RC_OK || out_cap == 0) return rc;
+    return run(c, ONC_K_DEFRAG_COPY, "defrag_copy", [&] { return onc::launch_defrag_copy(a, c->stream); });
 }
 
 int32_t onc_expected_message_len(const uint8_t* data, uint64_t len, uint32_t* out) {

@@ -29,6 +29,17 @@
 //                 verified stretches with 64-wide ballots.
 //   counts -> scan (len_tiles/scan_tiles/len_apply) -> frame_write: every
 //                 chunk on the chain re-chases its records writing rec_off.
+//
+// Fragment mode (onc_frame_fragments; the kFrag instances of frame_guess,
+// frame_chunks and frame_walk, everything after them shared): every mark
+// starts a fragment, whatever its last-fragment bit — the same loop without
+// the Fragmented test. Only a record's first fragment carries an RPC header
+// to guess by, so a chunk's chain runs on past its end, through chunks
+// without a guess and up to the guess of the next chunk that has one
+// (frame_chunks). The record-mode instances compile to the instruction
+// streams they had before the mode existed.
+#include <type_traits>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -65,22 +76,30 @@ struct GlobalStarts {       // straight to the chunk's slice of a.starts (the wa
 #define ONC_FRAME_CHUNKS_WG 64   // 512 waves spread over every CU: c2 framing chase 37.0 -> 34.6 us vs 256
 #endif
 constexpr int kChunksWG = ONC_FRAME_CHUNKS_WG;   // lanes (chunks) per frame_chunks workgroup
-struct LdsStarts {          // chunk-relative u32 in an LDS column (stride kChunksWG), copied out after the chase:
-    uint32_t* col;          // a global store inside the chase would hold up the next hop's load (one vmcnt)
+// chunk-relative offsets in an LDS column (stride kChunksWG), copied out after the chase: a global store
+// inside the chase would hold up the next hop's load (one vmcnt). u32 in record mode (a start lies in its
+// chunk); u64 in fragment mode, whose chase runs on past the chunk's end.
+template <class T>
+struct LdsStarts {
+    T* col;
     uint64_t c0;
-    __device__ __forceinline__ void operator()(uint32_t i, uint64_t p) const { col[i * kChunksWG] = uint32_t(p - c0); }
+    __device__ __forceinline__ void operator()(uint32_t i, uint64_t p) const { col[i * kChunksWG] = T(p - c0); }
 };
-template <class Sink>
-__device__ __forceinline__ Chase chase(const FrameArgs& a, uint64_t p, uint64_t lim, const Sink& rec) {
+// kFrag (onc_frame_fragments): every mark starts a fragment, whatever its
+// last-fragment bit says; the chain is the same loop without that test.
+// cnt0: starts already counted (and kept) by the chase this one goes on from.
+template <bool kFrag, class Sink>
+__device__ __forceinline__ Chase chase(const FrameArgs& a, uint64_t p, uint64_t lim, const Sink& rec,
+                                       uint32_t cnt0 = 0) {
     const uintptr_t base = reinterpret_cast<uintptr_t>(a.wire);
-    Chase c{p, 0, kExit, 0, 0};
+    Chase c{p, cnt0, kExit, 0, 0};
     while (p < lim) {
         if (a.len - p < 4) {                       // expected_message_len: rpc_message.rs:344-346
             c.st = ONC_ERR_INCOMPLETE_HEADER;
             break;
         }
         const uint32_t h = be_at(base, p);
-        if ((h & 0x80000000u) == 0) {              // :359-362
+        if (!kFrag && (h & 0x80000000u) == 0) {    // :359-362
             c.st = ONC_ERR_FRAGMENTED;
             break;
         }
@@ -106,13 +125,16 @@ __device__ __forceinline__ Chase chase(const FrameArgs& a, uint64_t p, uint64_t 
 // verifier length <= 200, or reply_stat 1 with a rejection kind 0/1. Every
 // record the reference's decoder accepts passes; the test only steers the
 // guess (a record that fails it is still framed, via the walk).
-template <class Be>
+// kFrag: the first fragment of a record carries the same header under a
+// mark with either last-fragment bit (a continuation fragment carries none:
+// it is never guessed, the chase before it runs through it).
+template <bool kFrag, class Be>
 __device__ __forceinline__ bool plausible_with(uint64_t len, uint64_t p, const Be& be) {
     const uint32_t h = be(0);
     const uint32_t mt = be(8);
     const uint32_t rv = be(12);
     const uint64_t want = uint64_t(h & 0x7FFFFFFFu) + 4;
-    if (!(h & 0x80000000u) || want < 24 || want > len - p) return false;
+    if ((!kFrag && !(h & 0x80000000u)) || want < 24 || want > len - p) return false;
     if (mt == 0) return rv == 2u && want >= 44 && be(32) <= ONC_MAX_AUTH_LEN;
     if (mt != 1 || rv > 1u) return false;
     const uint32_t w4 = be(16), w5 = be(20);
@@ -121,13 +143,22 @@ __device__ __forceinline__ bool plausible_with(uint64_t len, uint64_t p, const B
 
 __device__ __forceinline__ bool plausible_at(const FrameArgs& a, uint64_t p) {
     const uintptr_t base = reinterpret_cast<uintptr_t>(a.wire);
-    return plausible_with(a.len, p, [&](uint32_t k) { return be_at(base, p + k); });
+    return plausible_with<false>(a.len, p, [&](uint32_t k) { return be_at(base, p + k); });
+}
+// Fragment mode's second test of a candidate whose fragment ends at q: what
+// follows may be a continuation fragment, so only its mark is tested (the
+// fragment it announces lies within the buffer).
+__device__ __forceinline__ bool mark_fits_at(const FrameArgs& a, uint64_t q) {
+    if (a.len - q < 4) return false;
+    return uint64_t(be_at(reinterpret_cast<uintptr_t>(a.wire), q) & 0x7FFFFFFFu) + 4 <= a.len - q;
 }
 
 // 16-bit mask of the bytes of a 16-byte block (as four dwords) that could
 // start a record: high bit set (last-fragment flag of the record mark) and
 // three zero bytes at +8..+10 (message type 0 or 1 as a big-endian u32).
 // n = the next 16 bytes (for positions whose +8..+10 cross the block).
+// kFrag: without the high-bit test.
+template <bool kFrag>
 __device__ __forceinline__ uint32_t cand_mask16(const u32x4& v, const u32x4& n) {
     const uint32_t w[8] = {v.x, v.y, v.z, v.w, n.x, n.y, n.z, n.w};
     uint32_t hi = 0, zero = 0;                // bit k: byte k has the high bit / is zero (k < 32)
@@ -142,7 +173,7 @@ __device__ __forceinline__ uint32_t cand_mask16(const u32x4& v, const u32x4& n) 
             hi |= (((h >> 7) & 1u) | ((h >> 14) & 2u) | ((h >> 21) & 4u) | ((h >> 28) & 8u)) << (4 * i);
         }
     }
-    return hi & (zero >> 8) & (zero >> 9) & (zero >> 10) & 0xFFFFu;
+    return (kFrag ? 0xFFFFu : hi) & (zero >> 8) & (zero >> 9) & (zero >> 10) & 0xFFFFu;
 }
 
 // frame_guess: one wave per kGuessSub consecutive chunks (1 by default;
@@ -162,6 +193,7 @@ __device__ __forceinline__ uint32_t cand_mask16(const u32x4& v, const u32x4& n) 
 #endif
 constexpr int kGuessSub = ONC_GUESS_SUB;
 constexpr int kGuessWin = 272;            // dwords per staged step: 1 KiB + 64 B
+template <bool kFrag>
 __global__ __launch_bounds__(256) void frame_guess_kernel(FrameArgs a) {
     __shared__ uint32_t s_win[4][kGuessSub][kGuessWin];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -232,7 +264,7 @@ __global__ __launch_bounds__(256) void frame_guess_kernel(FrameArgs a) {
             const uint64_t hi_pos = min(c1, a.len >= 16 ? a.len - 15 : 0);   // candidates p < hi_pos
             const uint64_t o = blk[j] + 16ull * lane;
             const u32x4 nx = {w[4 * lane + 4], w[4 * lane + 5], w[4 * lane + 6], w[4 * lane + 7]};
-            uint32_t cand = cand_mask16(v[j], nx);
+            uint32_t cand = cand_mask16<kFrag>(v[j], nx);
             const uint64_t lo = c0 > o ? c0 - o : 0;
             const uint64_t hi = hi_pos > o ? min(uint64_t(16), hi_pos - o) : 0;
             cand &= (hi >= 16 ? 0xFFFFu : ((1u << hi) - 1u)) & (lo >= 16 ? 0u : ~((1u << lo) - 1u));
@@ -244,12 +276,12 @@ __global__ __launch_bounds__(256) void frame_guess_kernel(FrameArgs a) {
                     const uint32_t q = r + k, wi = q >> 2, sh = q & 3u;
                     return bswap(funnel(w[wi], sh ? w[wi + 1] : 0u, sh));
                 };
-                if (plausible_with(a.len, p, be_lds)) {
+                if (plausible_with<kFrag>(a.len, p, be_lds)) {
                     // and the record it claims is followed by another
                     // plausible start (or the buffer's end): rejects words
                     // inside a record that happen to look like a header
                     const uint64_t q = p + uint64_t(be_lds(0) & 0x7FFFFFFFu) + 4;
-                    if (q + 16 > a.len || plausible_at(a, q)) {
+                    if (kFrag ? (q == a.len || mark_fits_at(a, q)) : (q + 16 > a.len || plausible_at(a, q))) {
                         mine = p;
                         break;
                     }
@@ -286,8 +318,23 @@ __device__ __forceinline__ void put_chase(const FrameArgs& a, uint64_t t, const 
 // first_stop = the minimum flagged chunk. (The check reads only the guesses,
 // final before this launch, and the lane's own chase: one launch fewer than
 // a separate verification pass.)
+//
+// Fragment mode (kFrag): a chunk whose first fragment start is a
+// continuation fragment has its guess further in, or none, so a chain that
+// had to land on the next guess would fail at every such chunk. There the
+// lane's chain runs on past its chunk's end, through chunks without a guess
+// and through the part of a guessed chunk before its guess, until it lands
+// exactly on a guess (where that chunk's own chain takes over) or stops;
+// x / cnt / the kept starts cover that whole stretch. fail[t] = 1 when the
+// chain jumps over a guessed chunk or passes a guess without landing on it
+// (x = where it was then: a position of the chain all the same, from which
+// the walk goes on chunk by chunk). The induction is the record mode's: a
+// guessed chunk before the first failure is reached by the chain of the
+// guessed chunk before it.
+template <bool kFrag>
 __global__ __launch_bounds__(kChunksWG) void frame_chunks_kernel(FrameArgs a) {
-    __shared__ uint32_t s_rec[kStartsCap * kChunksWG];
+    using Rel = typename std::conditional<kFrag, uint64_t, uint32_t>::type;
+    __shared__ Rel s_rec[kStartsCap * kChunksWG];
     const uint64_t t = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (t >= a.nchunks) return;
     const uint64_t c0 = t * a.chunk;
@@ -297,9 +344,33 @@ __global__ __launch_bounds__(kChunksWG) void frame_chunks_kernel(FrameArgs a) {
     if (g == kNone) {
         put_chase(a, t, Chase{kNone, 0, kExit, 0, 0});
     } else {
-        const Chase c = chase(a, g, c1, LdsStarts{&s_rec[threadIdx.x], c0});
+        const LdsStarts<Rel> sink{&s_rec[threadIdx.x], c0};
+        Chase c = chase<kFrag>(a, g, c1, sink);
+        if constexpr (kFrag) {
+            uint64_t prev = t;                 // the chunk the chain was in last
+            while (c.st == kExit) {            // then c.x < len: chunk j exists
+                const uint64_t j = c.x / a.chunk;
+                for (uint64_t k = prev + 1; k < j && !bad; ++k)
+                    if (a.g[k] != kNone) bad = 1;
+                if (bad) break;
+                const uint64_t gj = a.g[j];
+                if (gj == c.x) break;          // landed on chunk j's guess
+                if ((gj != kNone && gj < c.x) || c.cnt >= 0x80000000u) {   // (cnt is 32 bits wide)
+                    bad = 1;
+                    break;
+                }
+                c = chase<kFrag>(a, c.x, gj != kNone ? gj : min((j + 1) * a.chunk, a.len), sink, c.cnt);
+                if (gj != kNone && c.st == kExit && c.x != gj) {
+                    bad = 1;
+                    break;
+                }
+                prev = j;
+            }
+            if (c.st != kExit) stop = 1;
+        }
         put_chase(a, t, c);
-        if (c.st == kExit) {
+        if constexpr (kFrag) {
+        } else if (c.st == kExit) {
             const uint64_t j = c.x / a.chunk;
             if (j >= a.nchunks || a.g[j] != c.x) bad = 1;
             for (uint64_t k = t + 1; k < j && !bad; ++k)
@@ -365,6 +436,9 @@ __device__ __forceinline__ uint64_t hier_find(const uint8_t* l1, const uint8_t* 
 // the next failing chunk (which is then on the chain, unless the chain
 // stops first); else re-chase t from E and step to the chunk its chain lands
 // in, clearing the guesses of chunks the record jumps over.
+// (Fragment mode: a chunk's stored chain may run past its end (frame_chunks);
+// a re-chase here stays inside its chunk, and the step after it is the same.)
+template <bool kFrag>
 __global__ __launch_bounds__(64) void frame_walk_kernel(FrameArgs a) {
     const int lane = threadIdx.x;
     const uint64_t f0 = *a.first_fail;
@@ -396,7 +470,7 @@ __global__ __launch_bounds__(64) void frame_walk_kernel(FrameArgs a) {
         }
         Chase c;
         if (g != E) {
-            c = chase(a, E, min((t + 1) * a.chunk, a.len),
+            c = chase<kFrag>(a, E, min((t + 1) * a.chunk, a.len),
                       GlobalStarts{lane == 0 ? a.starts + t * kStartsCap : nullptr});   // same in every lane
             if (lane == 0) {
                 a.g[t] = E;
@@ -544,20 +618,26 @@ __global__ __launch_bounds__(256) void frame_write_kernel(FrameArgs a) {
     }
 }
 
-hipError_t launch_frame_guess(const FrameArgs& a, hipStream_t s) {
+// frag: the fragment-mode instances (onc_frame_fragments); the count, scan
+// and write kernels are the same for both.
+hipError_t launch_frame_guess(const FrameArgs& a, hipStream_t s, bool frag) {
     const uint64_t waves = (a.nchunks + kGuessSub - 1) / kGuessSub;
-    ONC_LAUNCH(frame_guess_kernel, dim3(uint32_t((waves + 3) / 4)), dim3(256), 0, s, a);
+    const dim3 grid(uint32_t((waves + 3) / 4));
+    if (frag) ONC_LAUNCH(frame_guess_kernel<true>, grid, dim3(256), 0, s, a);
+    else ONC_LAUNCH(frame_guess_kernel<false>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_frame_chunks(const FrameArgs& a, hipStream_t s) {
+hipError_t launch_frame_chunks(const FrameArgs& a, hipStream_t s, bool frag) {
     const uint32_t blocks = uint32_t((a.nchunks + kChunksWG - 1) / kChunksWG);
-    ONC_LAUNCH(frame_chunks_kernel, dim3(blocks), dim3(kChunksWG), 0, s, a);
+    if (frag) ONC_LAUNCH(frame_chunks_kernel<true>, dim3(blocks), dim3(kChunksWG), 0, s, a);
+    else ONC_LAUNCH(frame_chunks_kernel<false>, dim3(blocks), dim3(kChunksWG), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_frame_walk(const FrameArgs& a, hipStream_t s) {
-    ONC_LAUNCH(frame_walk_kernel, dim3(1), dim3(64), 0, s, a);
+hipError_t launch_frame_walk(const FrameArgs& a, hipStream_t s, bool frag) {
+    if (frag) ONC_LAUNCH(frame_walk_kernel<true>, dim3(1), dim3(64), 0, s, a);
+    else ONC_LAUNCH(frame_walk_kernel<false>, dim3(1), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

@@ -8,6 +8,7 @@
 
 #include "../../include/onc_rpc.h"
 #include "common.h"
+#include "defrag_plan.h"
 
 namespace onc {
 
@@ -125,6 +126,27 @@ struct FrameArgs {
     uint64_t* first_stop;
 };
 
+// onc_defragment (defrag.hip). Scratch per fragment: E, S, off (8 bytes
+// each), M and the codec's record lengths (4 each): 32 bytes.
+struct DefragArgs {
+    const uint8_t* wire;
+    const uint64_t* frag_off;   // nfrag + 1
+    uint64_t nfrag;
+    uint8_t* out;           // the 16-byte aligned address at or below the caller's out
+    uint64_t origin;        // the caller's out from there (0..15)
+    uint64_t out_cap;       // the caller's capacity
+    uint64_t* rec_off;      // nfrag + 1
+    int32_t* status;        // nfrag
+    uint64_t* result;       // [6]
+    uint64_t* E;            // nfrag + 1: where a fragment's bytes start in `out` (origin included)
+    uint64_t* S;            // nfrag: where they start in `wire`
+    uint32_t* M;            // nfrag: the record's mark for its first fragment, else 0
+    uint32_t* lens;         // nfrag: record lengths, 0 past the last record
+    uint64_t* off;          // nfrag + 1: their scan
+    DefragAgg* blk;         // per 256 fragments (+ 1: the whole batch)
+    uint64_t* info;         // [0] n_multi, [1] start of the first record beyond the capacity
+};
+
 struct DecArgs {
     uint64_t n;
     const uint8_t* wire;
@@ -163,10 +185,10 @@ hipError_t launch_enc_emit(const EncArgs& a, hipStream_t s);
 hipError_t launch_iov_len(const IovArgs& a, hipStream_t s);
 hipError_t launch_iov_emit(const IovArgs& a, hipStream_t s);
 // frame.hip
-hipError_t launch_frame_walk(const FrameArgs& a, hipStream_t s);
+hipError_t launch_frame_walk(const FrameArgs& a, hipStream_t s, bool frag = false);
 hipError_t launch_frame_counts(const FrameArgs& a, hipStream_t s);
-hipError_t launch_frame_guess(const FrameArgs& a, hipStream_t s);
-hipError_t launch_frame_chunks(const FrameArgs& a, hipStream_t s);
+hipError_t launch_frame_guess(const FrameArgs& a, hipStream_t s, bool frag = false);
+hipError_t launch_frame_chunks(const FrameArgs& a, hipStream_t s, bool frag = false);
 hipError_t launch_frame_write(const FrameArgs& a, hipStream_t s);
 bool frame_fused_scan_ok(uint64_t nchunks);
 hipError_t launch_frame_cblk(const FrameArgs& a, uint64_t* blk_sum, hipStream_t s);
@@ -195,6 +217,12 @@ hipError_t launch_compact_iov_lens(const onc_iov_rec* iov, const int32_t* status
                                    hipStream_t s);
 hipError_t launch_compact_iov_apply(onc_iov_rec* iov, const int32_t* status, uint64_t n, const uint64_t* new_off,
                                     uint64_t* totals, hipStream_t s);
+// defrag.hip
+hipError_t launch_defrag_blk(const DefragArgs& a, hipStream_t s);
+hipError_t launch_defrag_blkscan(const DefragArgs& a, hipStream_t s);
+hipError_t launch_defrag_frag(const DefragArgs& a, hipStream_t s);
+hipError_t launch_defrag_place(const DefragArgs& a, hipStream_t s);
+hipError_t launch_defrag_copy(const DefragArgs& a, hipStream_t s);
 // decode.hip
 hipError_t launch_decode(const DecArgs& a, int mode, hipStream_t s);
 hipError_t launch_dlen_tiles(const uint32_t* rec_len, uint64_t n, uint64_t* tile_sum, uint64_t* blk_sum, hipStream_t s);

@@ -21,9 +21,11 @@ LIB_PATH = os.environ.get("ONC_RPC_AMD_LIB") or os.path.join(os.path.dirname(os.
 K_NAMES = ["enc_len_kernel", "scan_tiles_kernel", "enc_emit_kernel", "decode_kernel",
            "len_tiles_kernel", "len_apply_kernel", "iov_len_kernel", "iov_emit_kernel",
            "frame_chunks_kernel", "frame_write_kernel", "frame_walk_kernel",
-           "frame_counts_kernel", "frame_guess_kernel", "compact_kernels"]
+           "frame_counts_kernel", "frame_guess_kernel", "compact_kernels",
+           "defrag_plan_kernels", "defrag_copy_kernel"]
 (K_ENC_LEN, K_SCAN_TILES, K_ENC_EMIT, K_DEC_PARSE, K_LEN_TILES, K_LEN_APPLY, K_IOV_LEN,
- K_IOV_EMIT, K_FRAME, K_FRAME_WRITE, K_FRAME_WALK, K_FRAME_COUNTS, K_FRAME_GUESS, K_COMPACT) = range(14)
+ K_IOV_EMIT, K_FRAME, K_FRAME_WRITE, K_FRAME_WALK, K_FRAME_COUNTS, K_FRAME_GUESS, K_COMPACT,
+ K_DEFRAG_PLAN, K_DEFRAG_COPY) = range(16)
 ABI_VERSION = 8
 K_COUNT = len(K_NAMES)
 
@@ -38,6 +40,7 @@ EXPORTED = [
     "onc_codec_create_ex", "onc_codec_set_decode_policy", "onc_host_register", "onc_host_unregister",
     "onc_compact", "onc_compact_iov",
     "onc_decode_bounded", "onc_decode_lengths_bounded", "onc_decode_body_bounded",
+    "onc_frame_fragments", "onc_defragment",
 ]
 
 # onc_codec_options (include/onc_rpc.h)
@@ -117,6 +120,8 @@ def load_library(path=LIB_PATH):
     lib.onc_decode_bounded.argtypes = [vp, vp, u64, vp, u64, i32, C.POINTER(OncDecoded)]
     lib.onc_decode_lengths_bounded.argtypes = [vp, vp, u64, vp, u64, u64, i32, vp, C.POINTER(OncDecoded)]
     lib.onc_decode_body_bounded.argtypes = [vp, i32, vp, u64, vp, u64, i32, vp, C.POINTER(OncDecoded), vp]
+    lib.onc_frame_fragments.argtypes = [vp, vp, u64, vp, u64, vp]
+    lib.onc_defragment.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp]
     for name in EXPORTED:
         getattr(lib, name).restype = getattr(lib, name).restype or i32
     # a stale library would read a differently laid out onc_batch and label
@@ -291,6 +296,21 @@ class Codec:
         """Frame a stream of back-to-back records (device buffers)."""
         self._check(self.lib.onc_frame_stream(self.h, _ptr(wire), length, _ptr(rec_off), max_records,
                                               _ptr(result)), "onc_frame_stream")
+
+    def frame_fragments(self, wire, length, frag_off, max_frags, result):
+        """onc_frame_fragments: frame_stream at fragment level (every mark
+        starts a fragment, whatever its last-fragment bit)."""
+        self._check(self.lib.onc_frame_fragments(self.h, _ptr(wire), length, _ptr(frag_off), max_frags,
+                                                 _ptr(result)), "onc_frame_fragments")
+
+    def defragment(self, wire, frag_off, nfrag, out, rec_off, status, result, out_cap=None):
+        """onc_defragment: the framed fragments rebuilt as a packed stream of
+        single-fragment records in `out` (any byte address: a tensor or an
+        int device pointer with out_cap); result = 6 words."""
+        cap = out.numel() if out_cap is None else out_cap
+        optr = C.c_void_p(out) if isinstance(out, int) else _ptr(out)
+        self._check(self.lib.onc_defragment(self.h, _ptr(wire), _ptr(frag_off), nfrag, optr, cap, _ptr(rec_off),
+                                            _ptr(status), _ptr(result)), "onc_defragment")
 
     # -- decode -----------------------------------------------------------
     def decode(self, wire, rec_off, n, mode, msgs, unix, status, aux0, aux1):
@@ -517,6 +537,51 @@ def frame_host_stream(codec: Codec, buf: bytes, max_records=None, device="cuda")
     n = int(r[0])
     return (off.cpu().numpy().view(np.uint64)[:n + 1].copy(), n, int(r[1]), int(r[2]), int(np.uint32(r[3])),
             int(np.uint32(r[4])))
+
+
+def frame_host_fragments(codec: Codec, buf: bytes, max_frags=None, device="cuda"):
+    """frame_host_stream at fragment level -> (frag_off[n+1], n, consumed, status, aux0, aux1)."""
+    torch = _torch()
+    w = to_device(np.frombuffer(bytes(buf) + b"\0" * 16, np.uint8), device)
+    m = len(buf) // 4 + 1 if max_frags is None else max_frags
+    off = torch.zeros(m + 1, dtype=torch.int64, device=device)
+    res = torch.zeros(5, dtype=torch.int64, device=device)
+    codec.frame_fragments(w, len(buf), off, m, res)
+    codec.sync()
+    r = res.cpu().numpy()
+    n = int(r[0])
+    return (off.cpu().numpy().view(np.uint64)[:n + 1].copy(), n, int(r[1]), int(r[2]), int(np.uint32(r[3])),
+            int(np.uint32(r[4])))
+
+
+def reassemble_host_stream(codec: Codec, buf: bytes, device="cuda"):
+    """Convenience: host bytes of a stream of (possibly multi-fragment)
+    records -> onc_frame_fragments + onc_defragment -> (reassembled bytes,
+    rec_off[n+1], status[n], result[6], framing (n_frags, consumed, status,
+    aux0, aux1)), all on the host. The reassembled bytes are a packed stream
+    of single-fragment records: frame_host_stream / decode_host_wire take
+    them as they are."""
+    torch = _torch()
+    w = to_device(np.frombuffer(bytes(buf) + b"\0" * 16, np.uint8), device)
+    m = len(buf) // 4 + 1
+    frag_off = torch.zeros(m + 1, dtype=torch.int64, device=device)
+    fres = torch.zeros(5, dtype=torch.int64, device=device)
+    codec.frame_fragments(w, len(buf), frag_off, m, fres)
+    codec.sync()
+    fr = fres.cpu().numpy()
+    nfrag = int(fr[0])
+    # a reassembled record is never longer than its fragments
+    out = torch.zeros(max(16, (int(fr[1]) + 15) // 16 * 16), dtype=torch.uint8, device=device)
+    rec_off = torch.zeros(nfrag + 1, dtype=torch.int64, device=device)
+    status = torch.zeros(max(nfrag, 1), dtype=torch.int32, device=device)
+    res = torch.zeros(6, dtype=torch.int64, device=device)
+    codec.defragment(w, frag_off, nfrag, out, rec_off, status, res)
+    codec.sync()
+    r = res.cpu().numpy().view(np.uint64).copy()
+    n = int(r[0])
+    return (out.cpu().numpy()[:int(r[2])].tobytes(), rec_off.cpu().numpy().view(np.uint64)[:n + 1].copy(),
+            status.cpu().numpy()[:n].copy(), r,
+            (nfrag, int(fr[1]), int(fr[2]), int(np.uint32(fr[3])), int(np.uint32(fr[4]))))
 
 
 def codec_lengths(codec: Codec, db: DeviceBatch):
