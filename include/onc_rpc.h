@@ -76,7 +76,10 @@ extern "C" {
  *    onc_decode_body_bounded and the status ONC_DEC_BAD_EXTENT;
  *    onc_frame_fragments and onc_defragment (multi-fragment record streams)
  *    with the timing ids ONC_K_DEFRAG_PLAN / ONC_K_DEFRAG_COPY appended
- *    (ONC_K_COUNT 16: onc_codec_kernel_stats writes that many entries). */
+ *    (ONC_K_COUNT 16: onc_codec_kernel_stats writes that many entries);
+ *    onc_frame_streams (many connections' buffers framed in one call) and
+ *    onc_decode_extents (records that are not back to back), which add no
+ *    status code and no timing id. */
 #define ONC_RPC_ABI_VERSION 8
 
 /* ------------------------------------------------------------------------ */
@@ -422,7 +425,9 @@ int onc_codec_sync(onc_codec* codec);
  * keeps its own per-chunk scratch, sized by its first call on a stream that
  * long or longer (growing it inside a capture is ONC_RC_ECAPTURE too);
  * onc_frame_fragments shares it. onc_defragment of up to max_records
- * fragments is covered too (32 bytes of scratch per fragment). */
+ * fragments is covered too (32 bytes of scratch per fragment), and so is
+ * onc_frame_streams of up to max_records segments (under 100 bytes per
+ * segment). */
 int onc_codec_reserve(onc_codec* codec, uint64_t max_records);
 /* Map a caller's host buffer (a socket buffer: any malloc'd or mmap'd
  * range) for the kernels, so that an encode / decode reads and writes it in
@@ -471,7 +476,14 @@ int onc_abi_version(void);
  * the kernels they launch (ONC_K_ENC_LEN / _ENC_EMIT / _DEC_PARSE).
  * onc_frame_fragments launches at onc_frame_stream's sites (ONC_K_FRAME_*);
  * ONC_K_DEFRAG_PLAN is every planning launch of onc_defragment (its length
- * scan counts as onc_scan_lengths'), ONC_K_DEFRAG_COPY the byte copy. */
+ * scan counts as onc_scan_lengths'), ONC_K_DEFRAG_COPY the byte copy.
+ * onc_frame_streams and onc_decode_extents have no ids of their own: the
+ * per-segment chase (streams_chase) reports under ONC_K_FRAME, the scan of
+ * the segments' record counts under onc_scan_lengths' ids (ONC_K_LEN_TILES /
+ * ONC_K_LEN_APPLY, with ONC_K_SCAN_TILES beyond 8M segments), the write pass
+ * (streams_write) under ONC_K_FRAME_WRITE, the count of stopped segments
+ * (streams_result) under ONC_K_FRAME_COUNTS, and the extents decode under
+ * ONC_K_DEC_PARSE. */
 #define ONC_K_ENC_LEN      0
 #define ONC_K_SCAN_TILES   1
 #define ONC_K_ENC_EMIT     2
@@ -681,6 +693,81 @@ int onc_frame_fragments(onc_codec* codec, const uint8_t* wire, uint64_t len,
                         uint64_t* frag_off /*[dev, max_frags + 1]*/, uint64_t max_frags,
                         uint64_t* result /*[dev, 5]: n, consumed, status, aux0, aux1*/);
 
+/* Segmented framing: onc_frame_stream for many independent buffers at once —
+ * a server's per-connection receive buffers, usually slots of one pinned
+ * slab, each filled to its own level and holding a few whole records and
+ * often a cut one at the end. The reference anchor is the caller's loop of
+ * expected_message_len (src/rpc_message.rs:343-367) + one-message slices
+ * (rpc_message.rs:238-242), run once per connection. Segment s is
+ * wire[seg_off[s], seg_off[s] + seg_len[s]); segments may lie in any address
+ * order, start at any byte alignment and overlap (the wire is only read).
+ * seg_off / seg_len are trusted, as `len` is in onc_frame_stream;
+ * seg_len[s] < 2^34 (so a segment holds fewer than 2^32 records) and
+ * nseg < 2^32 are preconditions (nseg >= 2^32 is ONC_RC_EINVAL). The result
+ * is exactly that of
+ *
+ *   k = 0; needed = 0
+ *   for s in 0 .. nseg-1:
+ *       first = k; p = 0; st = ONC_OK; aux0 = aux1 = 0
+ *       while p < seg_len[s] and k < max_records:
+ *           left = seg_len[s] - p
+ *           if left < 4:  st = ONC_ERR_INCOMPLETE_HEADER; break
+ *           h = be32(wire, seg_off[s] + p)
+ *           if !(h >> 31): st = ONC_ERR_FRAGMENTED; break
+ *           want = (h & 0x7FFFFFFF) + 4
+ *           if left < want: st = ONC_ERR_INCOMPLETE_MESSAGE; aux0 = u32(left); aux1 = u32(want); break
+ *           rec_start[k] = seg_off[s] + p; rec_len[k] = want; rec_seg[k] = s; k++; p += want
+ *       seg_result[6s ..] = {first, k - first, p, st, aux0, aux1}
+ *       needed += records this segment frames when max_records is unbounded
+ *   result = {k, needed, number of segments whose st != ONC_OK}
+ *
+ *   rec_start[dev, max_records], rec_len[dev, max_records]: record k is
+ *                     wire[rec_start[k], rec_start[k] + rec_len[k]) — the
+ *                     extents onc_decode_extents takes. Records are ordered by
+ *                     segment index, then by position in the segment.
+ *   rec_seg[dev, max_records]: optional (may be NULL): the record's segment.
+ *   seg_result[dev, 6 * nseg]: per segment {first, n, consumed, status, aux0,
+ *                     aux1}: its records are [first, first + n), `consumed`
+ *                     bytes of it are framed (the caller memmoves the rest to
+ *                     the slot's start), and status says why it stopped there,
+ *                     as onc_frame_stream's does. An empty segment gives
+ *                     {first, 0, 0, ONC_OK, 0, 0}. A stopped segment (cut tail,
+ *                     fragmented mark, short header) affects nothing outside
+ *                     its own row.
+ *   result[dev, 3]  : {records framed, needed, segments whose status != ONC_OK}.
+ *                     `needed` = the records framed with unbounded
+ *                     max_records: the capacity a retry needs.
+ * Once max_records is reached, the segment being framed ends with status
+ * ONC_OK and its `consumed` is the start of its first unframed record; every
+ * later segment is {max_records, 0, 0, ONC_OK, 0, 0} (the caller's loop never
+ * looked at it). nseg == 0 or max_records == 0 writes a zero `result` and
+ * zeroes every seg_result row (first = 0). Entries of rec_start / rec_len /
+ * rec_seg at or past result[0] are not written. Asynchronous on the codec's
+ * stream.
+ * Memory access: only record marks are read — the aligned dwords holding the
+ * 4 bytes at each record start of a segment, never a byte of a payload and
+ * never an aligned dword without a segment byte — so framing a mapped host
+ * slab costs one small read per record (two for a segment of more than 16
+ * records, whose chain the write pass follows again).
+ * Kernels (streams.hip): every segment start is a certain record start, so
+ * there is no guess, no verification and no walk: a lane follows each
+ * segment's exact chain (onc_frame_stream's chase), the segments' record
+ * counts are scanned by onc_scan_lengths' launches, and a write pass fills
+ * the outputs — coalesced from the record lengths the chase kept (segments of
+ * up to 16 records), by a second chase otherwise. The design point is many
+ * segments of up to about a frame chunk (64 KiB) each; a longer segment is
+ * still exact but is followed serially by one lane: for one long stream use
+ * onc_frame_stream. A fragmented segment only reports ONC_ERR_FRAGMENTED in
+ * its row (onc_frame_fragments + onc_defragment on that segment's rest).
+ * Scratch: 96 bytes per segment (and 4 per 16 segments), covered by
+ * onc_codec_reserve(max_records >= nseg) — after it the call allocates
+ * nothing; growing it while the stream is capturing is ONC_RC_ECAPTURE. */
+int onc_frame_streams(onc_codec* codec, const uint8_t* wire,
+                      const uint64_t* seg_off, const uint64_t* seg_len, uint64_t nseg, /* [dev, nseg] each */
+                      uint64_t* rec_start, uint32_t* rec_len, uint32_t* rec_seg,       /* [dev, max_records]; rec_seg optional */
+                      uint64_t max_records,
+                      uint64_t* seg_result /* [dev, 6 * nseg] */, uint64_t* result /* [dev, 3] */);
+
 /* Rebuild framed fragments as the packed stream of single-fragment records
  * that RpcMessage::serialise_into writes (one mark with the last-fragment bit
  * and the total length, rpc_message.rs:156, then the body), so that
@@ -791,6 +878,26 @@ int onc_decode_lengths_bounded(onc_codec* codec, const uint8_t* wire, uint64_t w
 int onc_decode_body_bounded(onc_codec* codec, int root, const uint8_t* wire, uint64_t wire_len,
                             const uint64_t* rec_off, uint64_t n, int mode, const uint32_t* param,
                             const onc_decoded* out, uint32_t* consumed);
+
+/* Decode records that are not back to back: record i is
+ * wire[rec_start[i], rec_start[i] + rec_len[i]) — in any address order, with
+ * gaps or overlaps between records (onc_frame_streams' outputs: records of
+ * different connections' buffers, a cut tail or a slot's free space between
+ * them). Each is decoded exactly as onc_decode_bounded decodes that slice:
+ * status, aux words, the descriptor with wire offsets, and the AUTH_UNIX
+ * slots, which stay grouped per 64 *output* records from 128g. Always
+ * bounded: a record with rec_start[i] > wire_len, or rec_len[i] > wire_len -
+ * rec_start[i], gets ONC_DEC_BAD_EXTENT with aux0 = ONC_EXTENT_START_PAST_WIRE
+ * / ONC_EXTENT_END_PAST_WIRE (ONC_EXTENT_NOT_MONOTONIC cannot occur), a zeroed
+ * descriptor and no slot; the sum rec_start + rec_len is never formed and no
+ * byte is read for it. wire_len = UINT64_MAX is the way to trust the extents.
+ * Over-read rule, return codes and graph capture as onc_decode; no scratch.
+ * (A wave's loads go through one buffer resource based at its lowest record
+ * window — not at its first record's, as in the offset forms — so extents in
+ * descending address order keep the cooperative loaders.) */
+int onc_decode_extents(onc_codec* codec, const uint8_t* wire, uint64_t wire_len,
+                       const uint64_t* rec_start, const uint32_t* rec_len, uint64_t n,
+                       int mode, const onc_decoded* out);
 
 /* serialised_len() of every descriptor as `root` + the checks of that
  * root's serialise_into: shape (ONC_ENC_BAD_DESCRIPTOR), construction panics

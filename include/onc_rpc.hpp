@@ -688,6 +688,23 @@ private:
     size_t len_;
 };
 
+// One connection's receive buffer inside a slab (try_from_streams):
+// wire[off, off + len).
+struct Segment {
+    uint64_t off = 0, len = 0;
+};
+// What try_from_streams reports per segment: its records are results
+// [first, first + n), `consumed` bytes of it were framed (memmove the rest to
+// the buffer's start and read on), and why framing stopped there, as
+// try_from_stream's `stop` (ONC_OK: at the segment's end).
+struct SegmentResult {
+    uint64_t first = 0, n = 0, consumed = 0;
+    int32_t status = ONC_OK;
+    uint32_t aux0 = 0, aux1 = 0;
+    bool ok() const { return status == ONC_OK; }
+    Error error() const { return Error(status, aux0, aux1); }
+};
+
 // ----------------------------------------------------------------------------
 // BatchDecoder: try_from of many records (one buffer per record)
 // ----------------------------------------------------------------------------
@@ -720,7 +737,30 @@ public:
         return stream_at(codec, wire.host(), wire.dev(), wire.size(), mode, consumed, stop);
     }
 
+    // Many connections' receive buffers at once (slots of one slab, each
+    // filled to its own level): every segment framed on its own — the
+    // caller's expected_message_len loop per connection — and every whole
+    // record of every segment decoded, in two calls (onc_frame_streams,
+    // onc_decode_extents). Results are ordered by segment, then by position;
+    // per_segment (optional) receives one SegmentResult per segment. A cut
+    // tail or a fragmented mark stops only its own segment.
+    std::vector<Decoded> try_from_streams(Codec& codec, const uint8_t* wire, size_t wire_len,
+                                          const std::vector<Segment>& segments,
+                                          std::vector<SegmentResult>* per_segment = nullptr,
+                                          DecodeMode mode = DecodeMode::Slice) {
+        return streams_at(codec, wire, nullptr, wire_len, segments, per_segment, mode);
+    }
+    std::vector<Decoded> try_from_streams(Codec& codec, const HostRegistration& wire,
+                                          const std::vector<Segment>& segments,
+                                          std::vector<SegmentResult>* per_segment = nullptr,
+                                          DecodeMode mode = DecodeMode::Slice) {
+        return streams_at(codec, wire.host(), wire.dev(), wire.size(), segments, per_segment, mode);
+    }
+
 private:
+    std::vector<Decoded> streams_at(Codec& codec, const uint8_t* wire, const uint8_t* dev_wire, size_t wire_len,
+                                    const std::vector<Segment>& segments, std::vector<SegmentResult>* per_segment,
+                                    DecodeMode mode);
     // dev_wire: the kernels' address of `wire` (a registration), or null:
     // the wire is copied into the stage first
     std::vector<Decoded> lengths_at(Codec& codec, const uint8_t* wire, const uint8_t* dev_wire, size_t wire_len,
@@ -1163,6 +1203,67 @@ inline std::vector<Decoded> BatchDecoder::stream_at(Codec& codec, const uint8_t*
     const Out o = take_out(c, n);
     const onc_decoded d = o.dev();
     codec.check(onc_decode(codec.get(), wd, offd, n, int(mode), &d), "onc_decode");
+    codec.sync();
+    return results(o, n, wire);
+}
+
+inline std::vector<Decoded> BatchDecoder::streams_at(Codec& codec, const uint8_t* wire, const uint8_t* dev_wire,
+                                                     size_t wire_len, const std::vector<Segment>& segments,
+                                                     std::vector<SegmentResult>* per_segment, DecodeMode mode) {
+    using detail::need;
+    const size_t nseg = segments.size();
+    if (per_segment) per_segment->assign(nseg, SegmentResult{});
+    if (!nseg) return {};
+    // a segment must lie in the wire (the framer trusts its segment list);
+    // every record is at least 4 bytes
+    size_t max_records = 1;
+    for (const Segment& g : segments) {
+        if (g.off > wire_len || g.len > wire_len - g.off) throw CodecError("try_from_streams: segment outside the wire");
+        max_records += size_t(g.len / 4);
+    }
+    detail::Carve c{codec.stage((dev_wire ? 0 : need<uint8_t>(wire_len)) + 2 * need<uint64_t>(nseg) +
+                                need<uint64_t>(max_records) + need<uint32_t>(max_records) + need<uint64_t>(6 * nseg) +
+                                need<uint64_t>(3))};
+    const uint8_t* wd = dev_wire;
+    if (!dev_wire) {
+        const auto w = c.take<uint8_t>(wire_len);
+        if (wire_len) std::memcpy(w.host, wire, wire_len);
+        wd = w.dev;
+    }
+    const auto so = c.take<uint64_t>(nseg);
+    const auto sl = c.take<uint64_t>(nseg);
+    for (size_t i = 0; i < nseg; ++i) {
+        so.host[i] = segments[i].off;
+        sl.host[i] = segments[i].len;
+    }
+    const size_t start_at = c.off;
+    const auto start = c.take<uint64_t>(max_records);
+    const size_t len_at = c.off;
+    const auto len = c.take<uint32_t>(max_records);
+    const auto rows = c.take<uint64_t>(6 * nseg);
+    const auto res = c.take<uint64_t>(3);
+    codec.check(onc_frame_streams(codec.get(), wd, so.dev, sl.dev, nseg, start.dev, len.dev, nullptr, max_records,
+                                  rows.dev, res.dev),
+                "onc_frame_streams");
+    codec.sync();
+    if (per_segment) {
+        for (size_t i = 0; i < nseg; ++i) {
+            const uint64_t* r = rows.host + 6 * i;
+            (*per_segment)[i] = SegmentResult{r[0], r[1], r[2], int32_t(r[3]), uint32_t(r[4]), uint32_t(r[5])};
+        }
+    }
+    const size_t n = size_t(res.host[0]);
+    if (!n) return {};
+    // the outputs after what is staged (a stage that grows keeps the staged
+    // wire and extents; their device addresses move with it)
+    const size_t mark = c.off;
+    c.s = codec.stage(mark + out_bytes(n), mark);
+    if (!dev_wire) wd = c.s.dev;
+    const Out o = take_out(c, n);
+    const onc_decoded d = o.dev();
+    codec.check(onc_decode_extents(codec.get(), wd, wire_len, reinterpret_cast<const uint64_t*>(c.s.dev + start_at),
+                                   reinterpret_cast<const uint32_t*>(c.s.dev + len_at), n, int(mode), &d),
+                "onc_decode_extents");
     codec.sync();
     return results(o, n, wire);
 }

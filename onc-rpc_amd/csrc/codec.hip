@@ -55,6 +55,9 @@ struct onc_codec {
     // onc_defragment: the per-fragment plan (kernels.h DefragArgs)
     uint8_t* dfr = nullptr;
     uint64_t dfr_cap = 0;         // fragments
+    // onc_frame_streams: the per-segment chase state (kernels.h StreamsArgs)
+    uint8_t* stm = nullptr;
+    uint64_t stm_cap = 0;         // segments
     uint32_t timing = 0;   // bitmask of ONC_K_* ids whose launches are bracketed
     struct Pending {
         int kernel;
@@ -239,6 +242,31 @@ int ensure_defrag(onc_codec* c, uint64_t nfrag) {
     return ONC_RC_OK;
 }
 
+// onc_frame_streams' scratch for up to S segments: base (S + 1) and x as
+// u64, cnt, st, two aux words and kStreamKeep kept lengths as u32 — 96 bytes
+// per segment — and a count per write workgroup.
+uint64_t streams_bytes(uint64_t S) {
+    return 8 * (S + 2) * 2 + 4 * S * (4 + onc::kStreamKeep) + 4 * (onc::streams_write_groups(S) + 4);
+}
+int ensure_streams(onc_codec* c, uint64_t nseg) {
+    if (nseg <= c->stm_cap) return ONC_RC_OK;
+    if (capturing(c)) return refuse_in_capture(c);
+    const uint64_t want = std::max<uint64_t>(std::max<uint64_t>(nseg, 2 * c->stm_cap), 4096);
+    if (c->stm) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(c->stm);
+        c->stm = nullptr;
+        c->stm_cap = 0;
+    }
+    const hipError_t e = hipMalloc(&c->stm, streams_bytes(want));
+    if (e != hipSuccess) {
+        fail(c, e, "hipMalloc(streams scratch)");
+        return ONC_RC_ENOMEM;
+    }
+    c->stm_cap = want;
+    return ONC_RC_OK;
+}
+
 int set_device(onc_codec* c) {
     const hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return fail(c, e, "hipSetDevice");
@@ -319,6 +347,7 @@ int onc_codec_destroy(onc_codec* c) {
     if (c->cmp_off) (void)hipFree(c->cmp_off);
     if (c->cmp_bytes) (void)hipFree(c->cmp_bytes);
     if (c->dfr) (void)hipFree(c->dfr);
+    if (c->stm) (void)hipFree(c->stm);
     if (c->dec_hint_host) (void)hipHostFree(c->dec_hint_host);
     delete c;
     return ONC_RC_OK;
@@ -355,7 +384,11 @@ int onc_codec_reserve(onc_codec* c, uint64_t max_records) {
     if (rl != ONC_RC_OK) return rl;
     // onc_defragment of up to max_records fragments: its plan (the scan of
     // its record lengths, one per fragment at most, fits the scratch above)
-    return ensure_defrag(c, max_records);
+    const int rd = ensure_defrag(c, max_records);
+    if (rd != ONC_RC_OK) return rd;
+    // onc_frame_streams of up to max_records segments (the scan of their
+    // record counts fits the scratch above)
+    return ensure_streams(c, max_records);
 }
 
 // Host ranges onc_host_register pinned, process-wide (a pinned range belongs
@@ -952,6 +985,50 @@ int onc_frame_fragments(onc_codec* c, const uint8_t* wire, uint64_t len, uint64_
     return frame_stream(c, wire, len, frag_off, max_frags, result, true);
 }
 
+int onc_frame_streams(onc_codec* c, const uint8_t* wire, const uint64_t* seg_off, const uint64_t* seg_len,
+                      uint64_t nseg, uint64_t* rec_start, uint32_t* rec_len, uint32_t* rec_seg, uint64_t max_records,
+                      uint64_t* seg_result, uint64_t* result) {
+    if (!c || !result || nseg > 0xFFFFFFFFull) return ONC_RC_EINVAL;
+    if (nseg && (!seg_off || !seg_len || !seg_result)) return ONC_RC_EINVAL;
+    if (nseg && max_records && (!wire || !rec_start || !rec_len)) return ONC_RC_EINVAL;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    hipError_t e;
+    if (nseg == 0 || max_records == 0) {                  // nothing framed: every row {0, 0, 0, OK, 0, 0}
+        e = hipMemsetAsync(result, 0, 3 * sizeof(uint64_t), c->stream);
+        if (e == hipSuccess && nseg) e = hipMemsetAsync(seg_result, 0, 6 * nseg * sizeof(uint64_t), c->stream);
+        return e == hipSuccess ? ONC_RC_OK : fail(c, e, "hipMemsetAsync");
+    }
+    int rc = ensure_scratch(c, onc::num_tiles(nseg));
+    if (rc == ONC_RC_OK) rc = ensure_streams(c, nseg);
+    if (rc != ONC_RC_OK) return rc;
+    const uint64_t S = c->stm_cap;
+    onc::StreamsArgs a{};
+    a.wire = wire;
+    a.seg_off = seg_off;
+    a.seg_len = seg_len;
+    a.nseg = nseg;
+    a.max_records = max_records;
+    a.rec_start = rec_start;
+    a.rec_len = rec_len;
+    a.rec_seg = rec_seg;
+    a.seg_result = seg_result;
+    a.result = result;
+    a.base = reinterpret_cast<uint64_t*>(c->stm);
+    a.x = a.base + (S + 2);
+    a.cnt = reinterpret_cast<uint32_t*>(a.x + (S + 2));
+    a.st = reinterpret_cast<int32_t*>(a.cnt + S);
+    a.aux = a.cnt + 2 * S;
+    a.keep = a.cnt + 4 * S;
+    a.blk_stopped = a.keep + onc::kStreamKeep * S;
+    rc = run(c, ONC_K_FRAME, "streams_chase", [&] { return onc::launch_streams_chase(a, c->stream); });
+    // every segment's first record index, and their total (onc_scan_lengths' launches and timing ids)
+    if (rc == ONC_RC_OK) rc = onc_scan_lengths(c, a.cnt, nseg, 0, a.base);
+    if (rc != ONC_RC_OK) return rc;
+    rc = run(c, ONC_K_FRAME_WRITE, "streams_write", [&] { return onc::launch_streams_write(a, c->stream); });
+    if (rc != ONC_RC_OK) return rc;
+    return run(c, ONC_K_FRAME_COUNTS, "streams_result", [&] { return onc::launch_streams_result(a, c->stream); });
+}
+
 // The decode entry points and their bounded forms share one body each:
 // bounded = the wire-length checked kernels (decode.hip kBound, extent.h).
 static int decode_offsets(onc_codec* c, const uint8_t* wire, bool bounded, uint64_t wire_len, const uint64_t* rec_off,
@@ -981,6 +1058,27 @@ int onc_decode(onc_codec* c, const uint8_t* wire, const uint64_t* rec_off, uint6
 int onc_decode_bounded(onc_codec* c, const uint8_t* wire, uint64_t wire_len, const uint64_t* rec_off, uint64_t n,
                        int mode, const onc_decoded* out) {
     return decode_offsets(c, wire, true, wire_len, rec_off, n, mode, out);
+}
+
+int onc_decode_extents(onc_codec* c, const uint8_t* wire, uint64_t wire_len, const uint64_t* rec_start,
+                       const uint32_t* rec_len, uint64_t n, int mode, const onc_decoded* out) {
+    if (!c || !out || (mode != ONC_DECODE_SLICE && mode != ONC_DECODE_BYTES)) return ONC_RC_EINVAL;
+    if (n == 0) return ONC_RC_OK;
+    if (!rec_start || !rec_len || !out->msgs || !out->unix_params || !out->status || !out->aux0 || !out->aux1)
+        return ONC_RC_EINVAL;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    onc::DecArgs a{};
+    a.n = n;
+    a.wire = wire;
+    a.out = *out;
+    a.variant = c->variant;
+    a.bounded = 1;
+    a.wire_len = wire_len;
+    a.ext_start = rec_start;
+    a.ext_len = rec_len;
+    a.extents = 1;
+    decode_policy(c, a);
+    return run(c, ONC_K_DEC_PARSE, "decode", [&] { return onc::launch_decode(a, mode, c->stream); });
 }
 
 static int decode_lengths(onc_codec* c, const uint8_t* wire, bool bounded, uint64_t wire_len, const uint32_t* rec_len,

@@ -561,7 +561,28 @@ __device__ __forceinline__ uint32_t round1_chunks(uintptr_t win, uint32_t q0, ui
 // contiguous request rather than G (tools/link_lab.hip coop rows).
 // No branch separates the loads: under branches the compiler waited for
 // chunk 2 before issuing chunk 3.
-template <bool kLine, bool kCoop>
+#ifndef ONC_EXT_FIRST_BASE
+#define ONC_EXT_FIRST_BASE 0   // 1: lab build only (tools/streams_timing.py): the extents decode keeps the first-record base
+#endif
+// kMinBase (onc_decode_extents): the resource is based at the wave's lowest
+// window instead of its first record's. Extents come in any address order —
+// records of different connections' buffers — and a wave whose first record
+// is not its lowest would otherwise take the per-lane path at every such
+// boundary. That matters for the wire the call is for, a pinned host slab
+// (segments in descending order: 4.27 ms against 4.72 with the first-record
+// base); in device memory the per-lane loads are the faster ones (58 against
+// 65 us) — profiles/frame_streams_timing.log.
+__device__ __forceinline__ uintptr_t wave_min_window(uintptr_t win, bool active) {
+    unsigned long long v = active ? static_cast<unsigned long long>(win) : ~0ull;
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        const unsigned long long w = __shfl_xor(v, o, 64);
+        v = w < v ? w : v;
+    }
+    return uintptr_t(lane_u64(v, 0));
+}
+
+template <bool kLine, bool kCoop, bool kMinBase = false>
 __device__ __forceinline__ void load_round1(uint32_t* s_win, int t, uintptr_t win, uint32_t nch, u32x4 (&v)[kWin1L]) {
     constexpr uint32_t G = kLine ? kWin1L : kWin1;
     static_assert(kWin1 == 4 && kWin1L == 8, "pin lists below");
@@ -573,7 +594,7 @@ __device__ __forceinline__ void load_round1(uint32_t* s_win, int t, uintptr_t wi
     if (act == 0) return;
     const int first = __builtin_ctzll(act);
     // (lane_u64 zero-extends each half; a bare readlane is a signed int)
-    const uintptr_t rb = lane_u64(win, first);
+    const uintptr_t rb = kMinBase ? wave_min_window(win, nch != 0) : lane_u64(win, first);
     const bool near = nch == 0 || (win >= rb && win - rb < (uintptr_t(1) << 31) - 256);
     const uint32_t wo = uint32_t(win - rb);
     if (__ballot(!near) == 0) {
@@ -704,7 +725,7 @@ __device__ __forceinline__ uint32_t stage_round1(uint32_t* s_win, int t, uintptr
 // out-of-range offset (no request) — handed over through LDS rows [16, 32)
 // of the window (above round 1's staged rows). w[j - kR2] receives chunk j
 // of the lane's record for j in [nch, want), zeros elsewhere.
-template <bool kPolicy>
+template <bool kPolicy, bool kMinBase = false>
 __device__ __forceinline__ void load_round2_coop(uint32_t* s_win, int t, uintptr_t win, uint32_t nch, uint32_t want,
                                                  u32x4 (&w)[Round2<kPolicy>::kN2]) {
     constexpr uint32_t kR2 = Round2<kPolicy>::kR2, kN2 = Round2<kPolicy>::kN2;
@@ -715,7 +736,7 @@ __device__ __forceinline__ void load_round2_coop(uint32_t* s_win, int t, uintptr
     const uint64_t act = __ballot(r2);
     if (act == 0) return;
     const int first = __builtin_ctzll(act);
-    const uintptr_t rb = lane_u64(win, first);
+    const uintptr_t rb = kMinBase ? wave_min_window(win, r2) : lane_u64(win, first);
     const bool near = !r2 || (win >= rb && win - rb < (uintptr_t(1) << 31) - 256);
     if (__ballot(!near) != 0) {                        // windows too far apart: per-lane loads
 #pragma unroll
@@ -808,8 +829,9 @@ __device__ __forceinline__ uint32_t stage_round2(uint32_t* s_win, int t, uintptr
 }
 
 template <int MODE, bool kExact = false, bool kNTOut = false, bool kFromLen = false, bool kBlkFused = false,
-          bool kRoot = false, bool kLine = false, bool kBound = false>
+          bool kRoot = false, bool kLine = false, bool kBound = false, bool kExtents = false>
 __global__ __launch_bounds__(kDecTile) void decode_kernel(DecArgs a) {
+    static_assert(!kExtents || (kBound && !kFromLen && !kRoot), "extents: the bounded message decode only");
     __shared__ uint32_t s_win[kWinWords * kDecTile];
     static_assert(kWinWords * kDecTile * 4 >= kDecTile * sizeof(onc_msg), "descriptor staging reuses the window");
     const int t = threadIdx.x;
@@ -859,6 +881,13 @@ __global__ __launch_bounds__(kDecTile) void decode_kernel(DecArgs a) {
             a.rec_off_out[i] = b;
             if (i + 1 == a.n) a.rec_off_out[a.n] = b + L;
         }
+    } else if constexpr (kExtents) {
+        // onc_decode_extents: the record is where the caller says, wherever
+        // its neighbours are
+        if (valid) {
+            b = a.ext_start[i];
+            L = a.ext_len[i];
+        }
     } else if (valid) {
         b = a.rec_off[i];
         L = a.rec_off[i + 1] - b;
@@ -873,7 +902,8 @@ __global__ __launch_bounds__(kDecTile) void decode_kernel(DecArgs a) {
     uint32_t bad = kExtentOk;
     if constexpr (kBound) {
         if (valid)
-            bad = kFromLen ? extent_reason_len(a.base, b, L, a.wire_len) : extent_reason_off(b, b + L, a.wire_len);
+            bad = kExtents ? extent_reason(b, L, a.wire_len)      // (no sum b + L is formed)
+                  : kFromLen ? extent_reason_len(a.base, b, L, a.wire_len) : extent_reason_off(b, b + L, a.wire_len);
         if (bad != kExtentOk) b = L = 0;
     }
     const uintptr_t wire = reinterpret_cast<uintptr_t>(a.wire);
@@ -887,14 +917,14 @@ __global__ __launch_bounds__(kDecTile) void decode_kernel(DecArgs a) {
     uint32_t nch = 0, avail = 0, r44 = 0;
     if (L != 0) nch = round1_chunks<kLineP, kPolicy>(win, q0, L, avail, r44);
     u32x4 v1[kWin1L];
-    load_round1<kLineP, ONC_DEC_COOP>(s_win, t, win, nch, v1);
+    load_round1<kLineP, ONC_DEC_COOP, kExtents && !ONC_EXT_FIRST_BASE>(s_win, t, win, nch, v1);
     uint32_t want = 0, last = 0;
     if (L != 0) want = stage_round1<kLineP, kPolicy, kRoot>(s_win, t, base, q0, d0, L, needs2, v1, nch, avail, r44, last);
     // round 2 (headers longer than round 1): cooperative under the standard
     // policy (the whole wave), else per lane
     constexpr bool kCoop2 = ONC_DEC_COOP2 && kPolicy && !kLineP;
     u32x4 w2[Round2<kPolicy>::kN2];
-    if constexpr (kCoop2) load_round2_coop<kPolicy>(s_win, t, win, nch, want, w2);
+    if constexpr (kCoop2) load_round2_coop<kPolicy, kExtents && !ONC_EXT_FIRST_BASE>(s_win, t, win, nch, want, w2);
     if (L != 0 && want > nch) nch = stage_round2<kPolicy, kCoop2>(s_win, t, win, q0, d0, nch, want, last, w2);
     if constexpr (kPolicy) {
         // every 64th workgroup reports for the next launch how many of its
@@ -1085,7 +1115,20 @@ hipError_t launch_decode_any(const DecArgs& a, int mode, hipStream_t s) {
     return launch_message_decode<false, kBound>(a, mode, s);
 }
 
+// onc_decode_extents: the bounded message decode with the extents prologue
+// and the minimum-base loaders, per mode and first-round policy.
+template <bool kLine>
+hipError_t launch_extents_decode(const DecArgs& a, int mode, hipStream_t s) {
+    const dim3 g{uint32_t((a.n + kDecTile - 1) / kDecTile)}, b{uint32_t(kDecTile)};
+    if (mode == ONC_DECODE_BYTES)
+        ONC_LAUNCH((decode_kernel<ONC_DECODE_BYTES, true, true, false, false, false, kLine, true, true>), g, b, 0, s, a);
+    else
+        ONC_LAUNCH((decode_kernel<ONC_DECODE_SLICE, true, true, false, false, false, kLine, true, true>), g, b, 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_decode(const DecArgs& a, int mode, hipStream_t s) {
+    if (a.extents) return a.line ? launch_extents_decode<true>(a, mode, s) : launch_extents_decode<false>(a, mode, s);
     if (a.bounded) return launch_decode_any<true>(a, mode, s);
     return launch_decode_any<false>(a, mode, s);
 }

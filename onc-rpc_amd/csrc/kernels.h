@@ -171,6 +171,35 @@ struct DecArgs {
     // onc_decode*_bounded (last, so the fields above keep their kernarg offsets)
     uint32_t bounded;           // 1: the wire-length checked kernels (decode_kernel<..., kBound>)
     uint64_t wire_len;          // readable bytes from `wire`
+    // onc_decode_extents (appended: the fields above keep their kernarg offsets)
+    const uint64_t* ext_start;  // per record: its first byte's wire offset
+    const uint32_t* ext_len;    // per record: its length
+    uint32_t extents;           // 1: the extents kernels (decode_kernel<..., kExtents>; always bounded)
+};
+
+// onc_frame_streams (streams.hip). Scratch per segment: base and x (8 bytes
+// each), cnt, st and two aux words (4 each), kStreamKeep record lengths (4
+// each): 96 bytes; and 4 per write workgroup (kStreamKeep segments).
+constexpr uint32_t kStreamKeep = 16;   // record lengths the chase keeps per segment (= write lanes per segment)
+struct StreamsArgs {
+    const uint8_t* wire;
+    const uint64_t* seg_off;    // nseg
+    const uint64_t* seg_len;    // nseg
+    uint64_t nseg;
+    uint64_t max_records;
+    uint64_t* rec_start;        // max_records
+    uint32_t* rec_len;          // max_records
+    uint32_t* rec_seg;          // max_records, optional
+    uint64_t* seg_result;       // 6 * nseg
+    uint64_t* result;           // [3] framed, needed, segments stopped
+    // per segment, the unbounded chase (max_records does not enter it)
+    uint64_t* base;             // nseg + 1: exclusive scan of cnt (onc_scan_lengths); base[nseg] = needed
+    uint64_t* x;                // where the chain stops, relative to the segment
+    uint32_t* cnt;              // records of the segment
+    int32_t* st;                // why it stops (ONC_OK: at the segment's end)
+    uint32_t* aux;              // 2 per segment
+    uint32_t* keep;             // kStreamKeep per segment: its first records' lengths
+    uint32_t* blk_stopped;      // per streams_write workgroup: its segments that stopped
 };
 // the line policy when at least this many of a sampled workgroup's 64
 // records needed a second first-round window under the standard one
@@ -223,6 +252,11 @@ hipError_t launch_defrag_blkscan(const DefragArgs& a, hipStream_t s);
 hipError_t launch_defrag_frag(const DefragArgs& a, hipStream_t s);
 hipError_t launch_defrag_place(const DefragArgs& a, hipStream_t s);
 hipError_t launch_defrag_copy(const DefragArgs& a, hipStream_t s);
+// streams.hip
+hipError_t launch_streams_chase(const StreamsArgs& a, hipStream_t s);
+hipError_t launch_streams_write(const StreamsArgs& a, hipStream_t s);
+hipError_t launch_streams_result(const StreamsArgs& a, hipStream_t s);
+uint64_t streams_write_groups(uint64_t nseg);
 // decode.hip
 hipError_t launch_decode(const DecArgs& a, int mode, hipStream_t s);
 hipError_t launch_dlen_tiles(const uint32_t* rec_len, uint64_t n, uint64_t* tile_sum, uint64_t* blk_sum, hipStream_t s);

@@ -41,6 +41,7 @@ EXPORTED = [
     "onc_compact", "onc_compact_iov",
     "onc_decode_bounded", "onc_decode_lengths_bounded", "onc_decode_body_bounded",
     "onc_frame_fragments", "onc_defragment",
+    "onc_frame_streams", "onc_decode_extents",
 ]
 
 # onc_codec_options (include/onc_rpc.h)
@@ -122,6 +123,8 @@ def load_library(path=LIB_PATH):
     lib.onc_decode_body_bounded.argtypes = [vp, i32, vp, u64, vp, u64, i32, vp, C.POINTER(OncDecoded), vp]
     lib.onc_frame_fragments.argtypes = [vp, vp, u64, vp, u64, vp]
     lib.onc_defragment.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp]
+    lib.onc_frame_streams.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp]
+    lib.onc_decode_extents.argtypes = [vp, vp, u64, vp, vp, u64, i32, C.POINTER(OncDecoded)]
     for name in EXPORTED:
         getattr(lib, name).restype = getattr(lib, name).restype or i32
     # a stale library would read a differently laid out onc_batch and label
@@ -312,7 +315,24 @@ class Codec:
         self._check(self.lib.onc_defragment(self.h, _ptr(wire), _ptr(frag_off), nfrag, optr, cap, _ptr(rec_off),
                                             _ptr(status), _ptr(result)), "onc_defragment")
 
+    def frame_streams(self, wire, seg_off, seg_len, nseg, rec_start, rec_len, rec_seg, max_records, seg_result,
+                      result):
+        """onc_frame_streams: segment s = wire[seg_off[s], +seg_len[s]) framed
+        on its own, all in one call (rec_seg may be None); seg_result = 6
+        words per segment, result = 3 words."""
+        self._check(self.lib.onc_frame_streams(self.h, _ptr(wire), _ptr(seg_off), _ptr(seg_len), nseg,
+                                               _ptr(rec_start), _ptr(rec_len), _ptr(rec_seg), max_records,
+                                               _ptr(seg_result), _ptr(result)), "onc_frame_streams")
+
     # -- decode -----------------------------------------------------------
+    def decode_extents(self, wire, wire_len, rec_start, rec_len, n, mode, msgs, unix, status, aux0, aux1):
+        """onc_decode_extents: record i = wire[rec_start[i], +rec_len[i]), in
+        any order, bounded by wire_len (2**64 - 1: the extents are trusted)."""
+        d = OncDecoded(msgs.data_ptr(), unix.data_ptr(), status.data_ptr(), aux0.data_ptr(),
+                       aux1.data_ptr())
+        self._check(self.lib.onc_decode_extents(self.h, _ptr(wire), wire_len, _ptr(rec_start), _ptr(rec_len), n, mode,
+                                                C.byref(d)), "onc_decode_extents")
+
     def decode(self, wire, rec_off, n, mode, msgs, unix, status, aux0, aux1):
         d = OncDecoded(msgs.data_ptr(), unix.data_ptr(), status.data_ptr(), aux0.data_ptr(),
                        aux1.data_ptr())
@@ -552,6 +572,48 @@ def frame_host_fragments(codec: Codec, buf: bytes, max_frags=None, device="cuda"
     n = int(r[0])
     return (off.cpu().numpy().view(np.uint64)[:n + 1].copy(), n, int(r[1]), int(r[2]), int(np.uint32(r[3])),
             int(np.uint32(r[4])))
+
+
+def frame_host_streams(codec: Codec, slab, seg_off, seg_len, max_records=None, device="cuda", with_seg=True):
+    """Convenience: a host slab and its segments -> onc_frame_streams ->
+    (rec_start[n], rec_len[n], rec_seg[n] or None, seg_result[nseg, 6],
+    result[3]) on the host. max_records None: room for every mark the
+    segments can hold."""
+    torch = _torch()
+    w = to_device(np.frombuffer(bytes(slab) + b"\0" * 16, np.uint8), device)
+    so = np.ascontiguousarray(seg_off, np.uint64)
+    sl = np.ascontiguousarray(seg_len, np.uint64)
+    nseg = len(so)
+    m = int(sl.sum()) // 4 + 1 if max_records is None else max_records
+    d_so = torch.from_numpy(np.append(so, np.uint64(0)).view(np.int64).copy()).to(device)
+    d_sl = torch.from_numpy(np.append(sl, np.uint64(0)).view(np.int64).copy()).to(device)
+    start = torch.full((m + 1,), -1, dtype=torch.int64, device=device)
+    rlen = torch.full((m + 1,), -1, dtype=torch.int32, device=device)
+    rseg = torch.full((m + 1,), -1, dtype=torch.int32, device=device) if with_seg else None
+    rows = torch.full((6 * nseg + 1,), -1, dtype=torch.int64, device=device)
+    res = torch.full((3,), -1, dtype=torch.int64, device=device)
+    codec.frame_streams(w, d_so, d_sl, nseg, start, rlen, rseg, m, rows, res)
+    codec.sync()
+    r = res.cpu().numpy().view(np.uint64).copy()
+    n = int(r[0])
+    return (start.cpu().numpy().view(np.uint64)[:n].copy(), rlen.cpu().numpy().view(np.uint32)[:n].copy(),
+            rseg.cpu().numpy().view(np.uint32)[:n].copy() if with_seg else None,
+            rows.cpu().numpy().view(np.uint64)[:6 * nseg].reshape(nseg, 6).copy(), r)
+
+
+def decode_host_extents(codec: Codec, wire: np.ndarray, rec_start, rec_len, mode, wire_len=None, device="cuda"):
+    """Convenience: a host wire and extents -> onc_decode_extents -> host
+    arrays (wire_len None: the wire's size)."""
+    torch = _torch()
+    n = len(rec_start)
+    w = to_device(wire, device)
+    st = torch.from_numpy(np.append(np.asarray(rec_start, np.uint64), np.uint64(0)).view(np.int64).copy()).to(device)
+    ln = torch.from_numpy(np.append(np.asarray(rec_len, np.uint32), np.uint32(0)).view(np.int32).copy()).to(device)
+    bufs = DecodeBuffers(n, device)
+    codec.decode_extents(w, len(wire) if wire_len is None else wire_len, st, ln, n, mode, bufs.msgs, bufs.unix,
+                         bufs.status, bufs.aux0, bufs.aux1)
+    codec.sync()
+    return bufs.to_host()
 
 
 def reassemble_host_stream(codec: Codec, buf: bytes, device="cuda"):
