@@ -79,7 +79,9 @@ extern "C" {
  *    (ONC_K_COUNT 16: onc_codec_kernel_stats writes that many entries);
  *    onc_frame_streams (many connections' buffers framed in one call) and
  *    onc_decode_extents (records that are not back to back), which add no
- *    status code and no timing id. */
+ *    status code and no timing id; onc_fragment (records cut into fragments
+ *    on the send side), which reuses the existing status codes and
+ *    onc_defragment's timing ids. */
 #define ONC_RPC_ABI_VERSION 8
 
 /* ------------------------------------------------------------------------ */
@@ -425,7 +427,8 @@ int onc_codec_sync(onc_codec* codec);
  * keeps its own per-chunk scratch, sized by its first call on a stream that
  * long or longer (growing it inside a capture is ONC_RC_ECAPTURE too);
  * onc_frame_fragments shares it. onc_defragment of up to max_records
- * fragments is covered too (32 bytes of scratch per fragment), and so is
+ * fragments is covered too (32 bytes of scratch per fragment; onc_fragment
+ * of up to max_records records uses the same buffer), and so is
  * onc_frame_streams of up to max_records segments (under 100 bytes per
  * segment). */
 int onc_codec_reserve(onc_codec* codec, uint64_t max_records);
@@ -483,7 +486,9 @@ int onc_abi_version(void);
  * ONC_K_LEN_APPLY, with ONC_K_SCAN_TILES beyond 8M segments), the write pass
  * (streams_write) under ONC_K_FRAME_WRITE, the count of stopped segments
  * (streams_result) under ONC_K_FRAME_COUNTS, and the extents decode under
- * ONC_K_DEC_PARSE. */
+ * ONC_K_DEC_PARSE. onc_fragment has none either: its three plan launches
+ * report under ONC_K_DEFRAG_PLAN and its copy under ONC_K_DEFRAG_COPY (it
+ * launches no onc_scan_lengths kernel: its scan is 64 bits wide). */
 #define ONC_K_ENC_LEN      0
 #define ONC_K_SCAN_TILES   1
 #define ONC_K_ENC_EMIT     2
@@ -810,6 +815,67 @@ int onc_defragment(onc_codec* codec, const uint8_t* wire, const uint64_t* frag_o
                    uint8_t* out, uint64_t out_cap,
                    uint64_t* rec_off /*[dev, nfrag + 1]*/, int32_t* status /*[dev, nfrag]*/,
                    uint64_t* result /*[dev, 6]*/);
+
+/* The send side of RFC 5531 §11, the exact inverse of onc_defragment: every
+ * record of a packed stream cut into fragments of at most max_frag body
+ * bytes, as a sender that flushes through a bounded buffer writes them, or
+ * as a peer that caps the fragment size needs them. Record i is
+ * wire[rec_off[i], rec_off[i+1]): a single-fragment record as onc_encode,
+ * onc_defragment and onc_frame_stream delimit them. The extents are trusted,
+ * as in onc_decode; rec_off[0] may be any base. The record's own mark is
+ * never read: its body is the extent without its first four bytes,
+ * B = extent - 4. The result is exactly that of
+ *
+ *   pos = 0; nf = 0; multi = 0
+ *   for i in 0 .. n-1:
+ *       out_off[i] = pos; L = rec_off[i+1] - rec_off[i]
+ *       if L == 0: status[i] = ONC_OK; continue                  # a failing record's empty extent: nothing to send
+ *       if L < 4:  status[i] = ONC_ENC_BAD_DESCRIPTOR; continue  # no room for a mark; takes no bytes
+ *       B = L - 4; k = max(1, ceil(B / max_frag)); len = 4*k + B
+ *       status[i] = (pos <= out_cap and len <= out_cap - pos) ? ONC_OK : ONC_ENC_WRITE_ZERO
+ *       if OK: fragment j < k-1 = BE32(max_frag) ++ body[j*max_frag, +max_frag)
+ *              fragment k-1     = BE32(0x80000000 | (B - (k-1)*max_frag)) ++ the rest
+ *                                 (B == 0: the bare mark 80 00 00 00)
+ *       pos += len; nf += k; multi += (k > 1)                    # placement ignores out_cap, as onc_defragment
+ *   out_off[n] = pos; result = {nf, pos, multi}
+ *
+ *   max_frag        : the largest fragment body, 1 .. 0x7FFFFFFF (anything
+ *                     else is ONC_RC_EINVAL). With 0x7FFFFFFF and every
+ *                     B < 2^31 the output is the input byte for byte.
+ *   out_off[dev, n + 1]: where record i's fragments start in out;
+ *                     out_off[n] is the capacity the batch needs.
+ *   out[dev]        : any byte address (as onc_encode); must not overlap
+ *                     wire. A record that gets ONC_ENC_WRITE_ZERO writes none
+ *                     of its bytes, and neither does any record after it. No
+ *                     byte before out, at or after out + out_cap, or outside
+ *                     an OK record's extent is written.
+ *   status[dev, n]  : ONC_OK / ONC_ENC_BAD_DESCRIPTOR / ONC_ENC_WRITE_ZERO.
+ *   result[dev, 3]  : {fragments, out bytes (= out_off[n]), records of more
+ *                     than one fragment}; both counts include records beyond
+ *                     the capacity.
+ * B is not limited: this is how a body of 2^31 bytes or more, which
+ * serialise_into refuses (rpc_message.rs:146-151) and onc_defragment cannot
+ * write, gets sent at all. len can exceed 2^32 (max_frag = 1 gives 5 B), so
+ * bytes and fragments are scanned in 64 bits, not by onc_scan_lengths.
+ * Placeholders (failing records that keep an extent, ABI 7) are framable
+ * records and are fragmented like any other; a caller that wants the
+ * reference's stream runs onc_compact first.
+ * n == 0 gives out_off[0] = 0 and a zero result, and needs no wire, rec_off,
+ * status or out. Wire reads follow onc_decode's rule: only whole aligned
+ * 16-byte granules that hold bytes of a record with an extent of at least 4
+ * bytes. Asynchronous on the codec's stream. Scratch: under 32 bytes per
+ * record (8, and 24 per 256 records), whatever max_frag and the number of
+ * fragments are, in onc_defragment's buffer: onc_codec_reserve(max_records
+ * >= n) covers it; growing it inside a capture is ONC_RC_ECAPTURE.
+ * Kernels (fragment.hip): a plan over records (one 64-bit scan of {bytes,
+ * fragments, multi}) and a copy partitioned by output bytes in which
+ * fragment j of a record stands at the closed-form position j * (max_frag +
+ * 4): no per-fragment table and no search among fragments. */
+int onc_fragment(onc_codec* codec, const uint8_t* wire, const uint64_t* rec_off, uint64_t n,
+                 uint32_t max_frag,
+                 uint8_t* out, uint64_t out_cap,
+                 uint64_t* out_off /*[dev, n + 1]*/, int32_t* status /*[dev, n]*/,
+                 uint64_t* result /*[dev, 3]*/);
 
 /* Exclusive scan of record lengths into offsets:
  * rec_off[0] = base, rec_off[i+1] = rec_off[i] + rec_len[i]  ([dev]). */

@@ -1333,6 +1333,67 @@ inline Reassembled reassemble_stream(Codec& codec, const uint8_t* wire, size_t l
     return r;
 }
 
+// The send side: a packed stream of single-fragment records (what
+// BatchEncoder::serialise_into writes) cut on the device into fragments of at
+// most max_frag body bytes (onc_frame_stream + onc_fragment), as a sender
+// flushing a bounded buffer or a peer that caps the fragment size needs them.
+// reassemble_stream of `bytes` gives the input back.
+struct Fragmented {
+    std::vector<uint8_t> bytes;      // the fragmented stream (out_off.back() bytes)
+    std::vector<uint64_t> out_off;   // n + 1 offsets into bytes: where record i's fragments start
+    std::vector<int32_t> status;     // per record: ONC_OK
+    size_t n_frags = 0;              // fragments written
+    size_t n_multi = 0;              // records cut into more than one fragment
+    std::optional<Error> stop;       // why framing stopped before the buffer's end, if it did
+};
+
+inline Fragmented fragment_stream(Codec& codec, const uint8_t* stream, size_t len, uint32_t max_frag) {
+    using detail::need;
+    if (max_frag < 1 || max_frag > 0x7FFFFFFFu) throw CodecError("fragment_stream: max_frag outside 1 .. 0x7FFFFFFF");
+    Fragmented r;
+    r.out_off.assign(1, 0);
+    const size_t max_records = len / 4 + 1;
+    detail::Carve c{codec.stage(need<uint8_t>(len) + need<uint64_t>(max_records + 1) + need<uint64_t>(5))};
+    const auto w = c.take<uint8_t>(len);
+    if (len) std::memcpy(w.host, stream, len);
+    const size_t rec_at = c.off;
+    const auto rec = c.take<uint64_t>(max_records + 1);
+    const auto fres = c.take<uint64_t>(5);
+    codec.check(onc_frame_stream(codec.get(), w.dev, len, rec.dev, max_records, fres.dev), "onc_frame_stream");
+    codec.sync();
+    uint64_t f[5];
+    std::memcpy(f, fres.host, sizeof(f));
+    if (int32_t(f[2]) != ONC_OK) r.stop = Error(int32_t(f[2]), uint32_t(f[3]), uint32_t(f[4]));
+    const size_t n = size_t(f[0]);
+    if (!n) return r;
+    // every record is at least its mark: a mark more per further fragment
+    size_t cap = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint64_t body = rec.host[i + 1] - rec.host[i] - 4;
+        const uint64_t k = body / max_frag + (body % max_frag ? 1 : 0);
+        cap += size_t(body + 4 * (k ? k : 1));
+    }
+    // the outputs after what is staged (a stage that grows keeps it)
+    const size_t mark = c.off;
+    c.s = codec.stage(mark + need<uint8_t>(cap) + need<uint64_t>(n + 1) + need<int32_t>(n) + need<uint64_t>(3), mark);
+    const auto out = c.take<uint8_t>(cap);
+    const auto off = c.take<uint64_t>(n + 1);
+    const auto st = c.take<int32_t>(n);
+    const auto res = c.take<uint64_t>(3);
+    codec.check(onc_fragment(codec.get(), c.s.dev, reinterpret_cast<const uint64_t*>(c.s.dev + rec_at), n, max_frag,
+                             out.dev, cap, off.dev, st.dev, res.dev),
+                "onc_fragment");
+    codec.sync();
+    uint64_t d[3];
+    std::memcpy(d, res.host, sizeof(d));
+    r.bytes.assign(out.host, out.host + std::min<uint64_t>(d[1], cap));
+    r.out_off.assign(off.host, off.host + n + 1);
+    r.status.assign(st.host, st.host + n);
+    r.n_frags = size_t(d[0]);
+    r.n_multi = size_t(d[2]);
+    return r;
+}
+
 // ----------------------------------------------------------------------------
 // RpcMessage single-message forms (batches of one)
 // ----------------------------------------------------------------------------

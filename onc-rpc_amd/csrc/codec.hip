@@ -1355,6 +1355,46 @@ int onc_defragment(onc_codec* c, const uint8_t* wire, const uint64_t* frag_off, 
     return run(c, ONC_K_DEFRAG_COPY, "defrag_copy", [&] { return onc::launch_defrag_copy(a, c->stream); });
 }
 
+int onc_fragment(onc_codec* c, const uint8_t* wire, const uint64_t* rec_off, uint64_t n, uint32_t max_frag,
+                 uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status, uint64_t* result) {
+    if (!c || !out_off || !result || !onc::frag_max_ok(max_frag)) return ONC_RC_EINVAL;
+    if (n && (!wire || !rec_off || !status || (!out && out_cap))) return ONC_RC_EINVAL;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    if (n == 0) {
+        hipError_t e = hipMemsetAsync(result, 0, 3 * sizeof(uint64_t), c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(out_off, 0, sizeof(uint64_t), c->stream);
+        return e == hipSuccess ? ONC_RC_OK : fail(c, e, "hipMemsetAsync");
+    }
+    // onc_defragment's buffer, a record where it keeps a fragment: E (n + 1),
+    // then the info word and the block sums in its second array's place
+    int rc = ensure_defrag(c, n);
+    if (rc != ONC_RC_OK) return rc;
+    const uint64_t F = c->dfr_cap;
+    onc::FragmentArgs a{};
+    a.wire = wire;
+    a.rec_off = rec_off;
+    a.n = n;
+    a.max_frag = max_frag;
+    const uintptr_t oa = reinterpret_cast<uintptr_t>(out);
+    a.out = reinterpret_cast<uint8_t*>(oa & ~uintptr_t(15));
+    a.origin = oa & 15;
+    a.out_cap = out_cap;
+    a.out_off = out_off;
+    a.status = status;
+    a.result = result;
+    a.E = reinterpret_cast<uint64_t*>(c->dfr);
+    a.info = a.E + (F + 2);
+    a.blk = reinterpret_cast<onc::FragAgg*>(a.info + 2);
+    static_assert(sizeof(onc::FragAgg) == 24, "the block sums fit the second array: 24 (F / 256 + 2) + 16 <= 8 (F + 2)");
+    rc = run(c, ONC_K_DEFRAG_PLAN, "fragp_blk", [&] { return onc::launch_fragp_blk(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "fragp_blkscan", [&] { return onc::launch_fragp_blkscan(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "fragp_apply", [&] { return onc::launch_fragp_apply(a, c->stream); });
+    if (rc != ONC_RC_OK || out_cap == 0) return rc;
+    return run(c, ONC_K_DEFRAG_COPY, "frag_copy", [&] { return onc::launch_frag_copy(a, c->stream); });
+}
+
 int32_t onc_expected_message_len(const uint8_t* data, uint64_t len, uint32_t* out) {
     if (out) *out = 0;
     if (!data || len < 4) return ONC_ERR_INCOMPLETE_HEADER;          // rpc_message.rs:344-346

@@ -9,6 +9,7 @@
 #include "../../include/onc_rpc.h"
 #include "common.h"
 #include "defrag_plan.h"
+#include "fragment_plan.h"
 
 namespace onc {
 
@@ -147,6 +148,25 @@ struct DefragArgs {
     uint64_t* info;         // [0] n_multi, [1] start of the first record beyond the capacity
 };
 
+// onc_fragment (fragment.hip). Scratch per record: E (8 bytes) and the block
+// sums (24 per 256 records), in onc_defragment's buffer; the copy takes a
+// record's source and body length from the caller's rec_off.
+struct FragmentArgs {
+    const uint8_t* wire;
+    const uint64_t* rec_off;    // n + 1
+    uint64_t n;
+    uint32_t max_frag;      // 1 .. 0x7FFFFFFF
+    uint8_t* out;           // the 16-byte aligned address at or below the caller's out
+    uint64_t origin;        // the caller's out from there (0..15)
+    uint64_t out_cap;       // the caller's capacity
+    uint64_t* out_off;      // n + 1
+    int32_t* status;        // n
+    uint64_t* result;       // [3]
+    uint64_t* E;            // n + 1: where a record's fragments start in `out` (origin included)
+    FragAgg* blk;           // per 256 records (+ 1: the whole batch)
+    uint64_t* info;         // [0] start of the first record beyond the capacity
+};
+
 struct DecArgs {
     uint64_t n;
     const uint8_t* wire;
@@ -252,6 +272,11 @@ hipError_t launch_defrag_blkscan(const DefragArgs& a, hipStream_t s);
 hipError_t launch_defrag_frag(const DefragArgs& a, hipStream_t s);
 hipError_t launch_defrag_place(const DefragArgs& a, hipStream_t s);
 hipError_t launch_defrag_copy(const DefragArgs& a, hipStream_t s);
+// fragment.hip
+hipError_t launch_fragp_blk(const FragmentArgs& a, hipStream_t s);
+hipError_t launch_fragp_blkscan(const FragmentArgs& a, hipStream_t s);
+hipError_t launch_fragp_apply(const FragmentArgs& a, hipStream_t s);
+hipError_t launch_frag_copy(const FragmentArgs& a, hipStream_t s);
 // streams.hip
 hipError_t launch_streams_chase(const StreamsArgs& a, hipStream_t s);
 hipError_t launch_streams_write(const StreamsArgs& a, hipStream_t s);

@@ -42,6 +42,7 @@ EXPORTED = [
     "onc_decode_bounded", "onc_decode_lengths_bounded", "onc_decode_body_bounded",
     "onc_frame_fragments", "onc_defragment",
     "onc_frame_streams", "onc_decode_extents",
+    "onc_fragment",
 ]
 
 # onc_codec_options (include/onc_rpc.h)
@@ -124,6 +125,7 @@ def load_library(path=LIB_PATH):
     lib.onc_frame_fragments.argtypes = [vp, vp, u64, vp, u64, vp]
     lib.onc_defragment.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp]
     lib.onc_frame_streams.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp]
+    lib.onc_fragment.argtypes = [vp, vp, vp, u64, C.c_uint32, vp, u64, vp, vp, vp]
     lib.onc_decode_extents.argtypes = [vp, vp, u64, vp, vp, u64, i32, C.POINTER(OncDecoded)]
     for name in EXPORTED:
         getattr(lib, name).restype = getattr(lib, name).restype or i32
@@ -314,6 +316,16 @@ class Codec:
         optr = C.c_void_p(out) if isinstance(out, int) else _ptr(out)
         self._check(self.lib.onc_defragment(self.h, _ptr(wire), _ptr(frag_off), nfrag, optr, cap, _ptr(rec_off),
                                             _ptr(status), _ptr(result)), "onc_defragment")
+
+    def fragment(self, wire, rec_off, n, max_frag, out, out_off, status, result, out_cap=None):
+        """onc_fragment: the records wire[rec_off[i], rec_off[i+1]) cut into
+        fragments of at most max_frag body bytes in `out` (any byte address:
+        a tensor or an int device pointer with out_cap); out_off = n + 1
+        words, result = 3 words."""
+        cap = out.numel() if out_cap is None else out_cap
+        optr = C.c_void_p(out) if isinstance(out, int) else _ptr(out)
+        self._check(self.lib.onc_fragment(self.h, _ptr(wire), _ptr(rec_off), n, max_frag, optr, cap, _ptr(out_off),
+                                          _ptr(status), _ptr(result)), "onc_fragment")
 
     def frame_streams(self, wire, seg_off, seg_len, nseg, rec_start, rec_len, rec_seg, max_records, seg_result,
                       result):
@@ -644,6 +656,33 @@ def reassemble_host_stream(codec: Codec, buf: bytes, device="cuda"):
     return (out.cpu().numpy()[:int(r[2])].tobytes(), rec_off.cpu().numpy().view(np.uint64)[:n + 1].copy(),
             status.cpu().numpy()[:n].copy(), r,
             (nfrag, int(fr[1]), int(fr[2]), int(np.uint32(fr[3])), int(np.uint32(fr[4]))))
+
+
+def fragment_host(codec: Codec, wire_bytes, rec_off, max_frag, out_cap=None, shift=0, device="cuda"):
+    """Convenience: host bytes of a packed stream and its offsets ->
+    onc_fragment -> (the out_cap bytes from `out` on (out_cap None: the bytes
+    the batch needs), out_off[n+1], status[n], result[3]) on the host. `out`
+    starts `shift` bytes past a 16-byte aligned address and is zero-filled
+    before the call."""
+    torch = _torch()
+    ro = np.ascontiguousarray(rec_off, np.uint64)
+    n = len(ro) - 1
+    w = to_device(np.frombuffer(bytes(wire_bytes) + b"\0" * 16, np.uint8), device)
+    d_ro = torch.from_numpy(ro.view(np.int64).copy()).to(device)
+    out_off = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    status = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
+    res = torch.zeros(3, dtype=torch.int64, device=device)
+    cap = out_cap
+    if cap is None:                      # plan only: out_off[n] is what the batch needs
+        codec.fragment(w, d_ro, n, max_frag, 0, out_off, status, res, out_cap=0)
+        codec.sync()
+        cap = int(res.cpu().numpy().view(np.uint64)[1])
+    base = torch.zeros(16 + shift + cap + 16, dtype=torch.uint8, device=device)
+    lo = (-base.data_ptr()) % 16 + shift
+    codec.fragment(w, d_ro, n, max_frag, base.data_ptr() + lo, out_off, status, res, out_cap=cap)
+    codec.sync()
+    return (base.cpu().numpy()[lo:lo + cap].tobytes(), out_off.cpu().numpy().view(np.uint64).copy(),
+            status.cpu().numpy()[:n].copy(), res.cpu().numpy().view(np.uint64).copy())
 
 
 def codec_lengths(codec: Codec, db: DeviceBatch):
