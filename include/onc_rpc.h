@@ -428,8 +428,8 @@ int onc_codec_sync(onc_codec* codec);
  * long or longer (growing it inside a capture is ONC_RC_ECAPTURE too);
  * onc_frame_fragments shares it. onc_defragment of up to max_records
  * fragments is covered too (32 bytes of scratch per fragment; onc_fragment
- * of up to max_records records uses the same buffer), and so is
- * onc_frame_streams of up to max_records segments (under 100 bytes per
+ * and onc_fragment_iov of up to max_records records use the same buffer,
+ * under 32 bytes per record), and so is onc_frame_streams of up to max_records segments (under 100 bytes per
  * segment). */
 int onc_codec_reserve(onc_codec* codec, uint64_t max_records);
 /* Map a caller's host buffer (a socket buffer: any malloc'd or mmap'd
@@ -488,7 +488,8 @@ int onc_abi_version(void);
  * (streams_result) under ONC_K_FRAME_COUNTS, and the extents decode under
  * ONC_K_DEC_PARSE. onc_fragment has none either: its three plan launches
  * report under ONC_K_DEFRAG_PLAN and its copy under ONC_K_DEFRAG_COPY (it
- * launches no onc_scan_lengths kernel: its scan is 64 bits wide). */
+ * launches no onc_scan_lengths kernel: its scan is 64 bits wide), and so do
+ * onc_fragment_iov's three plan launches and its fill. */
 #define ONC_K_ENC_LEN      0
 #define ONC_K_SCAN_TILES   1
 #define ONC_K_ENC_EMIT     2
@@ -876,6 +877,92 @@ int onc_fragment(onc_codec* codec, const uint8_t* wire, const uint64_t* rec_off,
                  uint8_t* out, uint64_t out_cap,
                  uint64_t* out_off /*[dev, n + 1]*/, int32_t* status /*[dev, n]*/,
                  uint64_t* result /*[dev, 3]*/);
+
+/* onc_fragment for the vectored encode: the records of onc_encode_iov's (or
+ * onc_compact_iov's) list cut into fragments without a byte being copied.
+ * Fragmenting a vectored record needs no wire byte: its own mark is never
+ * read, every fragment mark is a function of the entry's two lengths and the
+ * limit, and every fragment body is one or two slices of memory that already
+ * exists. So the call reads only the entries of `iov` (never hdr_out or the
+ * payload arena, to which it takes no pointer; wire_off is ignored; the
+ * entries are trusted, as onc_fragment trusts rec_off) and writes 4 bytes per
+ * fragment into `marks` and a list of 16-byte pieces: gathering the pieces
+ * in order (a writev() list) is the fragmented stream. The result is exactly
+ * that of
+ *
+ *   pos = nf = multi = np = 0
+ *   for i in 0 .. n-1:
+ *       out_off[i] = pos; piece_off[i] = np
+ *       hl = iov[i].hdr_len; pl = iov[i].payload_len; L = hl + pl            # 64-bit
+ *       F = rec_max_frag ? rec_max_frag[i] : max_frag
+ *       if L == 0: status[i] = ONC_OK; continue                              # a failing record: nothing to send
+ *       if hl < 4 or F < 1 or F > 0x7FFFFFFF: status[i] = ONC_ENC_BAD_DESCRIPTOR; continue   # takes nothing
+ *       Hb = hl - 4; B = L - 4; k = max(1, ceil(B / F))
+ *       x = (Hb % F != 0 and pl > 0) ? 1 : 0                                 # one fragment holds header bytes, then payload bytes
+ *       e = (B == 0) ? 1 : 2k + x                                            # pieces of this record
+ *       fits = np <= max_pieces and e <= max_pieces - np and 4nf <= marks_cap and 4k <= marks_cap - 4nf
+ *       status[i] = fits ? ONC_OK : ONC_ENC_WRITE_ZERO
+ *       if fits: for j in 0 .. k-1:   [a, b) = [jF, min((j+1)F, B))
+ *           marks[4(nf+j) ..] = BE32((j == k-1 ? 0x80000000 : 0) | (b - a))
+ *           piece {MARK, 4(nf+j), 4}
+ *           if a < Hb and b > a:  piece {HDR, iov[i].hdr_off + 4 + a, min(b, Hb) - a}
+ *           if b > Hb and pl > 0: s = max(a, Hb); piece {PAYLOAD, iov[i].payload_off + s - Hb, b - s}
+ *       pos += 4k + B; nf += k; multi += (k > 1); np += e                    # placement ignores both capacities
+ *   out_off[n] = pos; piece_off[n] = np; result = {nf, pos, multi, np}
+ *
+ * A piece {src, off, len} is `len` bytes at byte `off` of `marks`
+ * (ONC_PIECE_MARK), of onc_encode_iov's hdr_out (ONC_PIECE_HDR) or of the
+ * batch's payload arena (ONC_PIECE_PAYLOAD); record i's pieces are
+ * pieces[piece_off[i], piece_off[i+1]) and stand for the stream bytes
+ * [out_off[i], out_off[i+1]).
+ *  - Equivalence with the packed path: when everything fits, the gathered
+ *    pieces are, byte for byte, what onc_fragment writes for onc_encode's
+ *    packed output of the same batch at the same max_frag; out_off, status
+ *    and result[0..2] are onc_fragment's.
+ *  - Capacity cut: placements only grow and a record that takes pieces also
+ *    takes marks, so the first ONC_ENC_WRITE_ZERO record and everything
+ *    after it write nothing. No piece at or past max_pieces is written and no
+ *    byte of marks at or past marks_cap.
+ *  - Needed capacities: result[3] pieces and 4 * result[0] bytes of marks
+ *    (a call with both capacities 0 is the plan alone).
+ *  - Zero-length pieces are never emitted. A placeholder (ABI 7) is a record
+ *    like any other; onc_compact_iov first gives the reference's stream.
+ *  - rec_max_frag[dev, n] (optional): a limit per record. NULL means the
+ *    uniform max_frag; when it is given max_frag is ignored but must still be
+ *    valid. A record whose own value is outside 1 .. 0x7FFFFFFF is
+ *    ONC_ENC_BAD_DESCRIPTOR and its neighbours are unaffected.
+ *  - ONC_RC_EINVAL: a NULL codec, out_off, piece_off or result; max_frag
+ *    outside 1 .. 0x7FFFFFFF; with n > 0 a NULL iov or status, NULL marks with
+ *    marks_cap > 0, NULL pieces with max_pieces > 0. ONC_RC_EALIGN: marks not
+ *    4-byte aligned or pieces not 16-byte aligned. n == 0 gives a zero result
+ *    and out_off[0] = piece_off[0] = 0 and needs nothing else.
+ * marks and pieces must not overlap iov, rec_max_frag or each other.
+ * All counts are 64 bits wide (hdr_len = payload_len = 0xFFFFFFFF at
+ * max_frag 1 is 2^33 fragments and 2^34 pieces). Asynchronous on the codec's
+ * stream. Scratch: under 32 bytes per record (16, and 32 per 256 records), in
+ * onc_defragment's buffer: onc_codec_reserve(max_records >= n) covers it;
+ * growing it inside a capture is ONC_RC_ECAPTURE. The three plan launches
+ * report under ONC_K_DEFRAG_PLAN and the fill under ONC_K_DEFRAG_COPY.
+ * Kernels (fragment_iov.hip): onc_fragment's plan with a fourth sum (pieces),
+ * and a fill partitioned by output pieces: a lane writes whole 16-byte pieces
+ * (and the mark of a MARK piece), its record found in a window of the sorted
+ * piece prefix staged in LDS, the piece's place inside the record by closed
+ * form (fragment_iov_plan.h): no per-fragment table and no search. */
+#define ONC_PIECE_MARK    0u   /* off: byte offset into `marks` */
+#define ONC_PIECE_HDR     1u   /* off: byte offset into onc_encode_iov's hdr_out */
+#define ONC_PIECE_PAYLOAD 2u   /* off: byte offset into the batch's payload arena */
+typedef struct onc_frag_piece {
+    uint64_t off;
+    uint32_t len;
+    uint32_t src;
+} onc_frag_piece;   /* 16 bytes */
+
+int onc_fragment_iov(onc_codec* codec, const onc_iov_rec* iov, uint64_t n,
+                     uint32_t max_frag, const uint32_t* rec_max_frag /*[dev, n], optional*/,
+                     uint8_t* marks, uint64_t marks_cap /*bytes*/,
+                     onc_frag_piece* pieces, uint64_t max_pieces,
+                     uint64_t* out_off /*[dev, n + 1]*/, uint64_t* piece_off /*[dev, n + 1]*/,
+                     int32_t* status /*[dev, n]*/, uint64_t* result /*[dev, 4]*/);
 
 /* Exclusive scan of record lengths into offsets:
  * rec_off[0] = base, rec_off[i+1] = rec_off[i] + rec_len[i]  ([dev]). */

@@ -27,7 +27,10 @@
 //
 // All codec work runs on the GPU through libonc_rpc_amd.so:
 //   BatchEncoder  — the caller's serialise_into loop over many messages,
-//                   one onc_encode_body call (one pass, no length pass).
+//                   one onc_encode_body call (one pass, no length pass);
+//                   serialise_vectored is its zero-copy form: headers only,
+//                   the records fragmented as a writev() list of pieces
+//                   (onc_encode_iov + onc_fragment_iov).
 //   BatchDecoder  — the caller's try_from loop over many records, one
 //                   onc_decode_lengths_bounded call (a record length that
 //                   runs past the wire is Error(ONC_DEC_BAD_EXTENT), unread).
@@ -590,6 +593,41 @@ private:
     MessageType message_;
 };
 
+// What BatchEncoder::serialise_vectored returns: the stream as a writev()
+// list. Piece i is pieces[i].len bytes at pieces[i].off of `marks`
+// (ONC_PIECE_MARK), of `headers` (ONC_PIECE_HDR) or of the encoder's payload
+// arena (ONC_PIECE_PAYLOAD); message m's pieces are
+// pieces[piece_off[m], piece_off[m + 1]) and stand for stream bytes
+// [out_off[m], out_off[m + 1]). A failing message has none.
+struct VectoredStream {
+    std::vector<uint8_t> headers;          // onc_encode_iov's hdr_out
+    std::vector<uint8_t> marks;            // 4 bytes per fragment
+    std::vector<onc_frag_piece> pieces;
+    std::vector<uint64_t> piece_off;       // n + 1
+    std::vector<uint64_t> out_off;         // n + 1
+    std::vector<int32_t> status;           // per message: ONC_OK or ONC_ENC_*
+    size_t n_frags = 0;                    // fragments (= marks.size() / 4)
+    size_t n_multi = 0;                    // messages cut into more than one fragment
+    uint64_t bytes = 0;                    // the stream's length (= out_off.back())
+
+    // (pointer, length) of piece i, as an iovec entry.
+    std::pair<const uint8_t*, size_t> piece_ptr(size_t i, const uint8_t* payload_arena) const {
+        const onc_frag_piece& p = pieces.at(i);
+        const uint8_t* base = p.src == ONC_PIECE_MARK ? marks.data() : p.src == ONC_PIECE_HDR ? headers.data() : payload_arena;
+        return {base + p.off, size_t(p.len)};
+    }
+    // The byte stream the pieces stand for.
+    std::vector<uint8_t> gather(const uint8_t* payload_arena) const {
+        std::vector<uint8_t> out;
+        out.reserve(size_t(bytes));
+        for (size_t i = 0; i < pieces.size(); ++i) {
+            const auto p = piece_ptr(i, payload_arena);
+            out.insert(out.end(), p.first, p.first + p.second);
+        }
+        return out;
+    }
+};
+
 // ----------------------------------------------------------------------------
 // BatchEncoder: serialise_into of many messages into one send buffer
 // ----------------------------------------------------------------------------
@@ -627,6 +665,16 @@ public:
                                         std::vector<uint64_t>* rec_off = nullptr);
     // serialised_len() of every pushed message (0 for failing ones).
     std::vector<uint32_t> serialised_lens(Codec& codec, std::vector<int32_t>* status = nullptr);
+    // The zero-copy form of serialise_into (RpcMessage batches only): only
+    // the headers are serialised (onc_encode_iov, then onc_compact_iov when a
+    // message fails), the payloads stay in this encoder's arena, and the
+    // records are cut into fragments of at most max_frag body bytes as a list
+    // of pieces (onc_fragment_iov) — nothing is copied. Throws CodecError for
+    // a body-level batch or a max_frag outside 1 .. 0x7FFFFFFF.
+    VectoredStream serialise_vectored(Codec& codec, uint32_t max_frag = 0x7FFFFFFFu);
+    // The payload bytes ONC_PIECE_PAYLOAD pieces point into: valid until the
+    // next push() or clear().
+    const std::vector<uint8_t>& payload_arena() const { return payload_; }
 
 private:
     // the batch's descriptors, AUTH_UNIX table and arenas copied into the
@@ -1050,6 +1098,77 @@ inline std::vector<int32_t> BatchEncoder::serialise_into(Codec& codec, std::vect
     }
     if (rec_off) *rec_off = std::move(off);
     return st;
+}
+
+// Headers into the stage (at most 1 KiB each, as above), then the plan alone
+// (both capacities 0) for the number of marks and pieces, then the fill into
+// a stage grown by exactly that (it keeps the entries; pointers re-derived).
+inline VectoredStream BatchEncoder::serialise_vectored(Codec& codec, uint32_t max_frag) {
+    using detail::need;
+    if (root() != ONC_ROOT_RPC_MESSAGE) throw CodecError("serialise_vectored: a body-level batch has no record marks");
+    if (max_frag < 1 || max_frag > 0x7FFFFFFFu) throw CodecError("serialise_vectored: max_frag outside 1 .. 0x7FFFFFFF");
+    const size_t n = msgs_.size();
+    VectoredStream r;
+    r.piece_off.assign(n + 1, 0);
+    r.out_off.assign(n + 1, 0);
+    r.status.assign(n, ONC_OK);
+    if (!n) return r;
+    const size_t hcap = 1024 * n;
+    detail::Carve c{codec.stage(staged_bytes() + need<uint8_t>(hcap) + need<onc_iov_rec>(n) + 2 * need<int32_t>(n) +
+                                2 * need<uint64_t>(n + 1) + need<uint64_t>(4))};
+    const onc_batch b = stage_batch(c);
+    const auto hdr = c.take<uint8_t>(hcap);
+    const size_t iov_at = c.off;
+    c.take<onc_iov_rec>(n);
+    const auto st = c.take<int32_t>(n);
+    const size_t fst_at = c.off;
+    c.take<int32_t>(n);
+    const size_t off_at = c.off;
+    c.take<uint64_t>(n + 1);
+    const size_t poff_at = c.off;
+    c.take<uint64_t>(n + 1);
+    const size_t res_at = c.off;
+    const auto res = c.take<uint64_t>(4);
+    auto iov = [&] { return reinterpret_cast<onc_iov_rec*>(c.s.dev + iov_at); };
+    codec.check(onc_encode_iov(codec.get(), &b, hdr.dev, hcap, iov(), st.dev, res.dev), "onc_encode_iov");
+    codec.sync();
+    std::memcpy(r.status.data(), st.host, n * 4);
+    r.headers.assign(hdr.host, hdr.host + size_t(res.host[0]));
+    // a failing message writes nothing: placeholder entries emptied (ABI 8)
+    for (size_t i = 0; i < n; ++i) {
+        if (r.status[i] != ONC_OK) {
+            codec.check(onc_compact_iov(codec.get(), iov(), st.dev, n, nullptr), "onc_compact_iov");
+            break;
+        }
+    }
+    auto fragment = [&](uint8_t* marks, uint64_t marks_cap, onc_frag_piece* pieces, uint64_t max_pieces) {
+        uint8_t* d = c.s.dev;
+        codec.check(onc_fragment_iov(codec.get(), iov(), n, max_frag, nullptr, marks, marks_cap, pieces, max_pieces,
+                                     reinterpret_cast<uint64_t*>(d + off_at), reinterpret_cast<uint64_t*>(d + poff_at),
+                                     reinterpret_cast<int32_t*>(d + fst_at), reinterpret_cast<uint64_t*>(d + res_at)),
+                    "onc_fragment_iov");
+        codec.sync();
+    };
+    fragment(nullptr, 0, nullptr, 0);
+    uint64_t d[4];
+    std::memcpy(d, c.s.host + res_at, sizeof(d));
+    const size_t nf = size_t(d[0]), np = size_t(d[3]);
+    const size_t kept = c.off;
+    c.s = codec.stage(kept + need<uint8_t>(4 * nf) + need<onc_frag_piece>(np), kept);
+    const auto marks = c.take<uint8_t>(4 * nf);
+    const auto pieces = c.take<onc_frag_piece>(np);
+    fragment(marks.dev, 4 * nf, pieces.dev, np);
+    const int32_t* fs = reinterpret_cast<const int32_t*>(c.s.host + fst_at);
+    for (size_t i = 0; i < n; ++i)
+        if (fs[i] != ONC_OK) throw CodecError(std::string("onc_fragment_iov: ") + onc_status_str(fs[i]));
+    r.marks.assign(marks.host, marks.host + 4 * nf);
+    r.pieces.assign(pieces.host, pieces.host + np);
+    std::memcpy(r.out_off.data(), c.s.host + off_at, (n + 1) * 8);
+    std::memcpy(r.piece_off.data(), c.s.host + poff_at, (n + 1) * 8);
+    r.n_frags = nf;
+    r.n_multi = size_t(d[2]);
+    r.bytes = d[1];
+    return r;
 }
 
 // ----------------------------------------------------------------------------

@@ -1395,6 +1395,53 @@ int onc_fragment(onc_codec* c, const uint8_t* wire, const uint64_t* rec_off, uin
     return run(c, ONC_K_DEFRAG_COPY, "frag_copy", [&] { return onc::launch_frag_copy(a, c->stream); });
 }
 
+int onc_fragment_iov(onc_codec* c, const onc_iov_rec* iov, uint64_t n, uint32_t max_frag, const uint32_t* rec_max_frag,
+                     uint8_t* marks, uint64_t marks_cap, onc_frag_piece* pieces, uint64_t max_pieces, uint64_t* out_off,
+                     uint64_t* piece_off, int32_t* status, uint64_t* result) {
+    if (!c || !out_off || !piece_off || !result || !onc::frag_max_ok(max_frag)) return ONC_RC_EINVAL;
+    if (n && (!iov || !status || (!marks && marks_cap) || (!pieces && max_pieces))) return ONC_RC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(marks) & 3) || (reinterpret_cast<uintptr_t>(pieces) & 15)) return ONC_RC_EALIGN;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    if (n == 0) {
+        hipError_t e = hipMemsetAsync(result, 0, 4 * sizeof(uint64_t), c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(out_off, 0, sizeof(uint64_t), c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(piece_off, 0, sizeof(uint64_t), c->stream);
+        return e == hipSuccess ? ONC_RC_OK : fail(c, e, "hipMemsetAsync");
+    }
+    // onc_defragment's buffer, a record where it keeps a fragment: P and NF
+    // (n + 1 each), then the info word and the block sums in its third
+    // array's place
+    int rc = ensure_defrag(c, n);
+    if (rc != ONC_RC_OK) return rc;
+    const uint64_t F = c->dfr_cap;
+    onc::FragmentIovArgs a{};
+    a.iov = iov;
+    a.n = n;
+    a.max_frag = max_frag;
+    a.rec_max_frag = rec_max_frag;
+    a.marks = marks;
+    a.marks_cap = marks_cap;
+    a.pieces = pieces;
+    a.max_pieces = max_pieces;
+    a.out_off = out_off;
+    a.piece_off = piece_off;
+    a.status = status;
+    a.result = result;
+    a.P = reinterpret_cast<uint64_t*>(c->dfr);
+    a.NF = a.P + (F + 2);
+    a.info = a.NF + (F + 2);
+    a.blk = reinterpret_cast<onc::FivAgg*>(a.info + 2);
+    static_assert(sizeof(onc::FivAgg) == 32, "the block sums fit the third array: 32 (F / 256 + 2) + 16 <= 8 (F + 2)");
+    rc = run(c, ONC_K_DEFRAG_PLAN, "fragiov_blk", [&] { return onc::launch_fragiov_blk(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "fragiov_blkscan", [&] { return onc::launch_fragiov_blkscan(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "fragiov_apply", [&] { return onc::launch_fragiov_apply(a, c->stream); });
+    // a record that takes a piece takes a mark: without room for one of each nothing is written
+    if (rc != ONC_RC_OK || max_pieces == 0 || marks_cap < 4) return rc;
+    return run(c, ONC_K_DEFRAG_COPY, "fragiov_fill", [&] { return onc::launch_fragiov_fill(a, c->stream); });
+}
+
 int32_t onc_expected_message_len(const uint8_t* data, uint64_t len, uint32_t* out) {
     if (out) *out = 0;
     if (!data || len < 4) return ONC_ERR_INCOMPLETE_HEADER;          // rpc_message.rs:344-346

@@ -9,6 +9,7 @@
 #include "../../include/onc_rpc.h"
 #include "common.h"
 #include "defrag_plan.h"
+#include "fragment_iov_plan.h"
 #include "fragment_plan.h"
 
 namespace onc {
@@ -167,6 +168,28 @@ struct FragmentArgs {
     uint64_t* info;         // [0] start of the first record beyond the capacity
 };
 
+// onc_fragment_iov (fragment_iov.hip). Scratch per record: P and NF (8 bytes
+// each) and the block sums (32 per 256 records), in onc_defragment's buffer;
+// the fill takes a record's lengths and sources from the caller's iov.
+struct FragmentIovArgs {
+    const onc_iov_rec* iov;     // n
+    uint64_t n;
+    uint32_t max_frag;          // 1 .. 0x7FFFFFFF
+    const uint32_t* rec_max_frag;   // n, or NULL: max_frag for every record
+    uint8_t* marks;             // 4-byte aligned
+    uint64_t marks_cap;         // bytes
+    onc_frag_piece* pieces;     // 16-byte aligned
+    uint64_t max_pieces;
+    uint64_t* out_off;          // n + 1
+    uint64_t* piece_off;        // n + 1
+    int32_t* status;            // n
+    uint64_t* result;           // [4]
+    uint64_t* P;                // n + 1: the pieces before a record (piece_off, read back by the fill)
+    uint64_t* NF;               // n + 1: the fragments before a record
+    FivAgg* blk;                // per 256 records (+ 1: the whole batch)
+    uint64_t* info;             // [0] first piece of the first record beyond a capacity
+};
+
 struct DecArgs {
     uint64_t n;
     const uint8_t* wire;
@@ -277,6 +300,11 @@ hipError_t launch_fragp_blk(const FragmentArgs& a, hipStream_t s);
 hipError_t launch_fragp_blkscan(const FragmentArgs& a, hipStream_t s);
 hipError_t launch_fragp_apply(const FragmentArgs& a, hipStream_t s);
 hipError_t launch_frag_copy(const FragmentArgs& a, hipStream_t s);
+// fragment_iov.hip
+hipError_t launch_fragiov_blk(const FragmentIovArgs& a, hipStream_t s);
+hipError_t launch_fragiov_blkscan(const FragmentIovArgs& a, hipStream_t s);
+hipError_t launch_fragiov_apply(const FragmentIovArgs& a, hipStream_t s);
+hipError_t launch_fragiov_fill(const FragmentIovArgs& a, hipStream_t s);
 // streams.hip
 hipError_t launch_streams_chase(const StreamsArgs& a, hipStream_t s);
 hipError_t launch_streams_write(const StreamsArgs& a, hipStream_t s);

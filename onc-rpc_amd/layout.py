@@ -83,6 +83,14 @@ IOV_DTYPE = np.dtype({
     "itemsize": 32,
 })
 assert MSG_DTYPE.itemsize == 64 and UNIX_DTYPE.itemsize == 96 and IOV_DTYPE.itemsize == 32
+# onc_frag_piece (onc_fragment_iov): `len` bytes at byte `off` of the source `src`
+FRAG_PIECE_DTYPE = np.dtype({
+    "names": ["off", "len", "src"],
+    "formats": ["<u8", "<u4", "<u4"],
+    "offsets": [0, 8, 12],
+    "itemsize": 16,
+})
+PIECE_MARK, PIECE_HDR, PIECE_PAYLOAD = 0, 1, 2
 
 
 def pack_kind_len(kind, length):

@@ -42,7 +42,7 @@ EXPORTED = [
     "onc_decode_bounded", "onc_decode_lengths_bounded", "onc_decode_body_bounded",
     "onc_frame_fragments", "onc_defragment",
     "onc_frame_streams", "onc_decode_extents",
-    "onc_fragment",
+    "onc_fragment", "onc_fragment_iov",
 ]
 
 # onc_codec_options (include/onc_rpc.h)
@@ -126,6 +126,7 @@ def load_library(path=LIB_PATH):
     lib.onc_defragment.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp]
     lib.onc_frame_streams.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp]
     lib.onc_fragment.argtypes = [vp, vp, vp, u64, C.c_uint32, vp, u64, vp, vp, vp]
+    lib.onc_fragment_iov.argtypes = [vp, vp, u64, C.c_uint32, vp, vp, u64, vp, u64, vp, vp, vp, vp]
     lib.onc_decode_extents.argtypes = [vp, vp, u64, vp, vp, u64, i32, C.POINTER(OncDecoded)]
     for name in EXPORTED:
         getattr(lib, name).restype = getattr(lib, name).restype or i32
@@ -326,6 +327,26 @@ class Codec:
         optr = C.c_void_p(out) if isinstance(out, int) else _ptr(out)
         self._check(self.lib.onc_fragment(self.h, _ptr(wire), _ptr(rec_off), n, max_frag, optr, cap, _ptr(out_off),
                                           _ptr(status), _ptr(result)), "onc_fragment")
+
+    def fragment_iov(self, iov, n, max_frag, marks, pieces, out_off, piece_off, status, result, rec_max_frag=None,
+                     marks_cap=None, max_pieces=None):
+        """onc_fragment_iov: the records of onc_encode_iov's list cut into
+        fragments of at most max_frag (or rec_max_frag[i]) body bytes with
+        nothing copied: 4 bytes per fragment into `marks` and 16-byte pieces
+        (layout.FRAG_PIECE_DTYPE) into `pieces` (uint8 tensors, None or int
+        device pointers with a capacity); out_off and piece_off = n + 1
+        words, result = 4 words."""
+        def arg(t, cap, unit):
+            if t is None:
+                return None, (0 if cap is None else cap)
+            if isinstance(t, int):
+                return C.c_void_p(t), cap
+            return _ptr(t), (t.numel() * t.element_size() // unit if cap is None else cap)
+        mp, mcap = arg(marks, marks_cap, 1)
+        pp, pcap = arg(pieces, max_pieces, 16)
+        self._check(self.lib.onc_fragment_iov(self.h, _ptr(iov), n, max_frag, _ptr(rec_max_frag), mp, mcap, pp, pcap,
+                                              _ptr(out_off), _ptr(piece_off), _ptr(status), _ptr(result)),
+                    "onc_fragment_iov")
 
     def frame_streams(self, wire, seg_off, seg_len, nseg, rec_start, rec_len, rec_seg, max_records, seg_result,
                       result):
@@ -683,6 +704,57 @@ def fragment_host(codec: Codec, wire_bytes, rec_off, max_frag, out_cap=None, shi
     codec.sync()
     return (base.cpu().numpy()[lo:lo + cap].tobytes(), out_off.cpu().numpy().view(np.uint64).copy(),
             status.cpu().numpy()[:n].copy(), res.cpu().numpy().view(np.uint64).copy())
+
+
+def fragment_iov_host(codec: Codec, iov, max_frag, rec_max_frag=None, marks_cap=None, max_pieces=None, device="cuda"):
+    """Convenience: a host array of onc_iov_rec (layout.IOV_DTYPE) ->
+    onc_fragment_iov -> (marks uint8[marks_cap], pieces
+    FRAG_PIECE_DTYPE[max_pieces], out_off[n+1], piece_off[n+1], status[n],
+    result[4]) on the host. A capacity left None is what the batch needs (a
+    plan-only call with both capacities 0 finds it); both buffers are
+    zero-filled before the call."""
+    torch = _torch()
+    e = np.ascontiguousarray(iov, L.IOV_DTYPE)
+    n = len(e)
+    d_iov = to_device(e, device)
+    d_lim = None
+    if rec_max_frag is not None:
+        d_lim = torch.from_numpy(np.append(np.asarray(rec_max_frag, np.uint32), np.uint32(0)).view(np.int32).copy()
+                                 ).to(device)
+    out_off = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    piece_off = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    status = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
+    res = torch.zeros(4, dtype=torch.int64, device=device)
+    if marks_cap is None or max_pieces is None:
+        codec.fragment_iov(d_iov, n, max_frag, None, None, out_off, piece_off, status, res, rec_max_frag=d_lim)
+        codec.sync()
+        r = res.cpu().numpy().view(np.uint64)
+        marks_cap = 4 * int(r[0]) if marks_cap is None else marks_cap
+        max_pieces = int(r[3]) if max_pieces is None else max_pieces
+    marks = torch.zeros(marks_cap + 16, dtype=torch.uint8, device=device)
+    pieces = torch.zeros(16 * max_pieces + 16, dtype=torch.uint8, device=device)
+    codec.fragment_iov(d_iov, n, max_frag, marks, pieces, out_off, piece_off, status, res, rec_max_frag=d_lim,
+                       marks_cap=marks_cap, max_pieces=max_pieces)
+    codec.sync()
+    return (marks.cpu().numpy()[:marks_cap].copy(),
+            pieces.cpu().numpy()[:16 * max_pieces].view(L.FRAG_PIECE_DTYPE).copy(),
+            out_off.cpu().numpy().view(np.uint64).copy(), piece_off.cpu().numpy().view(np.uint64).copy(),
+            status.cpu().numpy()[:n].copy(), res.cpu().numpy().view(np.uint64).copy())
+
+
+def gather_pieces(pieces, marks, hdr, payload_arena):
+    """The byte stream a writev() of `pieces` sends: every piece's slice of
+    its source (host arrays: onc_fragment_iov's marks, onc_encode_iov's
+    hdr_out, the batch's payload arena), in order."""
+    ln = pieces["len"].astype(np.int64)
+    at = np.arange(int(ln.sum())) - np.repeat(np.cumsum(ln) - ln, ln) + np.repeat(pieces["off"].astype(np.int64), ln)
+    which = np.repeat(pieces["src"], ln)
+    out = np.empty(len(at), np.uint8)
+    for s, a in enumerate((marks, hdr, payload_arena)):
+        m = which == s
+        if m.any():
+            out[m] = np.asarray(a, np.uint8)[at[m]]
+    return out.tobytes()
 
 
 def codec_lengths(codec: Codec, db: DeviceBatch):
