@@ -81,7 +81,9 @@ extern "C" {
  *    onc_decode_extents (records that are not back to back), which add no
  *    status code and no timing id; onc_fragment (records cut into fragments
  *    on the send side), which reuses the existing status codes and
- *    onc_defragment's timing ids. */
+ *    onc_defragment's timing ids; onc_frame_fragment_streams and
+ *    onc_defragment_extents (fragmented records of many connections
+ *    reassembled in one call), which add no status code and no timing id. */
 #define ONC_RPC_ABI_VERSION 8
 
 /* ------------------------------------------------------------------------ */
@@ -430,6 +432,9 @@ int onc_codec_sync(onc_codec* codec);
  * fragments is covered too (32 bytes of scratch per fragment; onc_fragment
  * and onc_fragment_iov of up to max_records records use the same buffer,
  * under 32 bytes per record), and so is onc_frame_streams of up to max_records segments (under 100 bytes per
+ * segment). onc_defragment_extents is covered as onc_defragment is, and
+ * onc_frame_fragment_streams of up to max_records segments as
+ * onc_frame_streams is (the two share one buffer of under 112 bytes per
  * segment). */
 int onc_codec_reserve(onc_codec* codec, uint64_t max_records);
 /* Map a caller's host buffer (a socket buffer: any malloc'd or mmap'd
@@ -489,7 +494,13 @@ int onc_abi_version(void);
  * ONC_K_DEC_PARSE. onc_fragment has none either: its three plan launches
  * report under ONC_K_DEFRAG_PLAN and its copy under ONC_K_DEFRAG_COPY (it
  * launches no onc_scan_lengths kernel: its scan is 64 bits wide), and so do
- * onc_fragment_iov's three plan launches and its fill. */
+ * onc_fragment_iov's three plan launches and its fill.
+ * onc_frame_fragment_streams reports under the ids onc_frame_streams uses:
+ * its chase (fragstreams_chase) under ONC_K_FRAME, its two scans (fragment
+ * counts, record counts) under onc_scan_lengths' ids, its write pass
+ * (fragstreams_write) under ONC_K_FRAME_WRITE and its result
+ * (fragstreams_result) under ONC_K_FRAME_COUNTS. onc_defragment_extents
+ * reports as onc_defragment does (ONC_K_DEFRAG_PLAN / ONC_K_DEFRAG_COPY). */
 #define ONC_K_ENC_LEN      0
 #define ONC_K_SCAN_TILES   1
 #define ONC_K_ENC_EMIT     2
@@ -764,7 +775,10 @@ int onc_frame_fragments(onc_codec* codec, const uint8_t* wire, uint64_t len,
  * segments of up to about a frame chunk (64 KiB) each; a longer segment is
  * still exact but is followed serially by one lane: for one long stream use
  * onc_frame_stream. A fragmented segment only reports ONC_ERR_FRAGMENTED in
- * its row (onc_frame_fragments + onc_defragment on that segment's rest).
+ * its row: the rests {seg_off + consumed, seg_len - consumed} of all such
+ * rows go through onc_frame_fragment_streams + onc_defragment_extents in one
+ * call each (or one segment's rest through onc_frame_fragments +
+ * onc_defragment).
  * Scratch: 96 bytes per segment (and 4 per 16 segments), covered by
  * onc_codec_reserve(max_records >= nseg) — after it the call allocates
  * nothing; growing it while the stream is capturing is ONC_RC_ECAPTURE. */
@@ -816,6 +830,118 @@ int onc_defragment(onc_codec* codec, const uint8_t* wire, const uint64_t* frag_o
                    uint8_t* out, uint64_t out_cap,
                    uint64_t* rec_off /*[dev, nfrag + 1]*/, int32_t* status /*[dev, nfrag]*/,
                    uint64_t* result /*[dev, 6]*/);
+
+/* onc_frame_streams at fragment level: the fragments of many connections'
+ * buffers in one call (RFC 5531 §11; the reference rejects such records:
+ * Error::Fragmented, rpc_message.rs:359-362). Per segment the fragment chain
+ * is followed as onc_frame_fragments follows it, and the fragments of the
+ * segment's complete records come out as scattered extents — what
+ * onc_defragment_extents takes. The segments are onc_frame_streams': any
+ * order, any alignment, overlapping allowed, trusted; seg_len[s] < 2^34 and
+ * nseg < 2^32 are preconditions (nseg >= 2^32 is ONC_RC_EINVAL). Fragment k
+ * is wire[frag_start[k], frag_start[k] + frag_len[k]), its mark included
+ * (frag_len >= 4; the largest value, 0x80000003, fits 32 bits). Only
+ * fragments of complete records are emitted — a record is complete when its
+ * run of fragments ends inside the segment with a mark whose bit 31 is set —
+ * so every emitted run ends with a last fragment and no record spans two
+ * segments. The result is exactly that of
+ *
+ *   k = r = needed = stopped = 0; full = false
+ *   for s in 0 .. nseg-1:
+ *       if full: seg_result[8s ..] = {max_frags, 0, 0, ONC_OK, 0, 0, 0, 0}
+ *                (still add this segment's complete-record fragments to needed); continue
+ *       # the walk: max_frags does not enter it
+ *       p = 0; st = ONC_OK; aux0 = aux1 = 0; open = []; recs = []
+ *       while p < seg_len[s]:
+ *           left = seg_len[s] - p
+ *           if left < 4: st = ONC_ERR_INCOMPLETE_HEADER; break
+ *           h = be32(wire, seg_off[s] + p); want = (h & 0x7FFFFFFF) + 4
+ *           if left < want: st = ONC_ERR_INCOMPLETE_MESSAGE; aux0 = u32(left); aux1 = u32(want); break
+ *           open.append((p, want)); p += want
+ *           if h >> 31: recs.append(open); open = []
+ *       needed += fragments in recs                 # `open` (the pending run) is never emitted nor counted
+ *       # the commit: whole records while they fit
+ *       first = k; first_rec = r; consumed = 0; cut = false
+ *       for R in recs:
+ *           if len(R) > max_frags - k: cut = full = true; break
+ *           for (fp, fl) in R: frag_start[k] = seg_off[s] + fp; frag_len[k] = fl; frag_seg[k] = s; k++
+ *           r++; consumed = end of R
+ *       seg_result[8s ..] = {first, k - first, consumed, cut ? ONC_OK : st, cut ? 0 : aux0, cut ? 0 : aux1, first_rec, r - first_rec}
+ *       stopped += (row status != ONC_OK)
+ *   result = {k, needed, r, stopped}
+ *
+ *   frag_start[dev, max_frags], frag_len[dev, max_frags]: the extents, ordered
+ *                     by segment index, then by position in the segment.
+ *   frag_seg[dev, max_frags]: optional (may be NULL): the fragment's segment.
+ *   seg_result[dev, 8 * nseg]: per segment {first, n, consumed, status, aux0,
+ *                     aux1, first_rec, n_rec}: its fragments are [first,
+ *                     first + n), they make the records [first_rec, first_rec +
+ *                     n_rec) of onc_defragment_extents' output, and `consumed`
+ *                     bytes of it are done with: the end of its last emitted
+ *                     record.
+ *   result[dev, 4]  : {fragments emitted, needed, records emitted, segments
+ *                     whose status != ONC_OK}. `needed` = the fragments emitted
+ *                     with unbounded max_frags: the capacity a retry needs.
+ * ONC_ERR_FRAGMENTED is never reported. A segment that ends on a fragment
+ * boundary in the middle of a record has status ONC_OK and consumed <
+ * seg_len: the caller moves [consumed, seg_len) down and waits for the rest,
+ * as it does for a cut tail (INCOMPLETE_MESSAGE / INCOMPLETE_HEADER, whose
+ * pending run is not emitted either). A stopped or pending segment affects
+ * nothing outside its own row. The segment at which the capacity runs out
+ * emits its records while they fit whole and has status ONC_OK; the segments
+ * after it get the row {max_frags, 0, 0, ONC_OK, 0, 0, 0, 0}, because the
+ * caller's loop never looked at them. nseg == 0 or max_frags == 0 writes a
+ * zero `result` and zero rows. Entries of frag_start / frag_len / frag_seg at
+ * or past result[0] are not written. Zero-length fragments and bare last
+ * marks (80 00 00 00: an empty record) are legal anywhere. Asynchronous on
+ * the codec's stream.
+ * Memory access follows onc_frame_streams' rule: only the aligned dwords
+ * holding a mark are read — no fragment body byte, and no dword without a
+ * segment byte (two reads per mark for a segment with more than 16 fragments
+ * in complete records, whose chain the write pass follows again).
+ * Use: onc_frame_streams on the slab first — single-fragment peers stay on
+ * the in-place path, nothing copied; for every row with ONC_ERR_FRAGMENTED put
+ * {seg_off + consumed, seg_len - consumed} into a second segment list, run
+ * this call and onc_defragment_extents on that list, then onc_decode on the
+ * rebuilt stream. A list of all connections is legal too: a single-fragment
+ * record is a one-fragment record.
+ * Kernels (streams.hip): onc_frame_streams' structure, every segment start
+ * being a certain fragment start — a lane follows each segment's chain and
+ * commits at every last fragment, the segments' fragment and record counts
+ * are scanned by onc_scan_lengths' launches (twice), and a write pass fills
+ * the outputs, coalesced from the marks the chase kept or by a second chase.
+ * The argument checks and ONC_RC_ECAPTURE are onc_frame_streams'. Scratch:
+ * 108 bytes per segment (and 4 per 16 segments), in onc_frame_streams'
+ * buffer, covered by onc_codec_reserve(max_records >= nseg). */
+int onc_frame_fragment_streams(onc_codec* codec, const uint8_t* wire,
+                               const uint64_t* seg_off, const uint64_t* seg_len, uint64_t nseg, /* [dev, nseg] each */
+                               uint64_t* frag_start, uint32_t* frag_len, uint32_t* frag_seg,    /* [dev, max_frags]; frag_seg optional */
+                               uint64_t max_frags,
+                               uint64_t* seg_result /* [dev, 8 * nseg] */, uint64_t* result /* [dev, 4] */);
+
+/* onc_defragment for fragments that are not back to back (it relates to
+ * onc_defragment as onc_decode_extents relates to onc_decode): fragment j is
+ * wire[frag_start[j], frag_start[j] + frag_len[j]), its mark included —
+ * onc_frame_fragment_streams' outputs, in any address order. With C = the
+ * concatenation of the fragments in order and frag_off = the prefix sums of
+ * frag_len, `out`, rec_off and status are those of onc_defragment(C,
+ * frag_off, nfrag, ...), and so is result, except that result[1] is the
+ * number of fragments consumed (nfrag - pending_frags) instead of a byte
+ * offset. Everything else is onc_defragment's: the extents are trusted
+ * (frag_len >= 4 is a precondition); trailing fragments without a last mark
+ * are counted, not emitted; out may be any byte address and must not overlap
+ * the fragments; nothing is written outside the OK records' extents;
+ * ONC_ENC_TOO_LONG and ONC_ENC_WRITE_ZERO apply as there; wire reads are
+ * limited to the whole aligned 16-byte granules that hold fragment bytes;
+ * nfrag == 0 gives rec_off[0] = 0 and a zero result. Scratch: 32 bytes per
+ * fragment, covered by onc_codec_reserve(max_records >= nfrag); timing ids
+ * ONC_K_DEFRAG_PLAN / ONC_K_DEFRAG_COPY. The output is the packed stream plus
+ * rec_off: onc_decode and everything after it apply unchanged. */
+int onc_defragment_extents(onc_codec* codec, const uint8_t* wire,
+                           const uint64_t* frag_start, const uint32_t* frag_len, uint64_t nfrag,
+                           uint8_t* out, uint64_t out_cap,
+                           uint64_t* rec_off /*[dev, nfrag + 1]*/, int32_t* status /*[dev, nfrag]*/,
+                           uint64_t* result /*[dev, 6]*/);
 
 /* The send side of RFC 5531 §11, the exact inverse of onc_defragment: every
  * record of a packed stream cut into fragments of at most max_frag body

@@ -53,6 +53,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <iterator>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -753,6 +754,20 @@ struct SegmentResult {
     Error error() const { return Error(status, aux0, aux1); }
 };
 
+// What try_from_mixed_streams returns: one result list per connection, in
+// stream order, whether its peer fragments its records or not.
+struct MixedStreams {
+    std::vector<std::vector<Decoded>> per_connection;
+    // per connection: n = its results, `consumed` bytes of its buffer are done
+    // with (memmove the rest down and read on), status why it stopped there
+    // (ONC_OK: at the buffer's end, or on a fragment boundary inside a record
+    // whose last fragment has not arrived); `first` is not used
+    std::vector<SegmentResult> segments;
+    // the records of the fragmenting peers, reassembled: their results' payload
+    // views point here (the others' into the caller's wire)
+    std::vector<uint8_t> reassembled;
+};
+
 // ----------------------------------------------------------------------------
 // BatchDecoder: try_from of many records (one buffer per record)
 // ----------------------------------------------------------------------------
@@ -804,6 +819,14 @@ public:
                                           DecodeMode mode = DecodeMode::Slice) {
         return streams_at(codec, wire.host(), wire.dev(), wire.size(), segments, per_segment, mode);
     }
+
+    // The same for a server some of whose peers fragment their records (RFC
+    // 5531 §11): try_from_streams first — single-fragment peers are decoded in
+    // place — then the rests of the segments that stopped with
+    // ONC_ERR_FRAGMENTED reassembled in one pass (reassemble_streams:
+    // onc_frame_fragment_streams + onc_defragment_extents) and decoded.
+    MixedStreams try_from_mixed_streams(Codec& codec, const uint8_t* wire, size_t wire_len,
+                                        const std::vector<Segment>& segments, DecodeMode mode = DecodeMode::Slice);
 
 private:
     std::vector<Decoded> streams_at(Codec& codec, const uint8_t* wire, const uint8_t* dev_wire, size_t wire_len,
@@ -1450,6 +1473,138 @@ inline Reassembled reassemble_stream(Codec& codec, const uint8_t* wire, size_t l
     r.pending_body_bytes = size_t(d[4]);
     r.n_multi = size_t(d[5]);
     return r;
+}
+
+// The same for many connections' buffers at once (segments of one slab, as
+// BatchDecoder::try_from_streams takes them): the fragments of every segment's
+// complete records found in one call (onc_frame_fragment_streams) and rebuilt
+// in one call (onc_defragment_extents) as one packed stream of single-fragment
+// records, ordered by segment. A segment's records are [first_rec, first_rec +
+// n_rec) of rec_off; `consumed` bytes of it are done with — up to the end of
+// its last complete record: a pending run stays in the buffer — and status
+// says why its walk stopped (ONC_OK: at its end or on a fragment boundary).
+struct SegmentRecords {
+    uint64_t first_rec = 0, n_rec = 0, consumed = 0;
+    int32_t status = ONC_OK;
+    uint32_t aux0 = 0, aux1 = 0;
+    bool ok() const { return status == ONC_OK; }
+    Error error() const { return Error(status, aux0, aux1); }
+};
+struct ReassembledStreams {
+    std::vector<uint8_t> bytes;      // the reassembled stream (rec_off.back() bytes)
+    std::vector<uint64_t> rec_off;   // n + 1 offsets into bytes
+    std::vector<int32_t> status;     // per record: ONC_OK or ONC_ENC_TOO_LONG
+    size_t n_frags = 0;              // fragments the records came in
+    size_t n_multi = 0;              // records that came in more than one fragment
+};
+
+inline ReassembledStreams reassemble_streams(Codec& codec, const uint8_t* wire, size_t wire_len,
+                                             const std::vector<Segment>& segments,
+                                             std::vector<SegmentRecords>* per_segment = nullptr) {
+    using detail::need;
+    ReassembledStreams r;
+    r.rec_off.assign(1, 0);
+    const size_t nseg = segments.size();
+    if (per_segment) per_segment->assign(nseg, SegmentRecords{});
+    if (!nseg) return r;
+    // a segment must lie in the wire (the framer trusts its segment list);
+    // every fragment is at least 4 bytes
+    size_t max_frags = 1;
+    for (const Segment& g : segments) {
+        if (g.off > wire_len || g.len > wire_len - g.off) throw CodecError("reassemble_streams: segment outside the wire");
+        max_frags += size_t(g.len / 4);
+    }
+    detail::Carve c{codec.stage(need<uint8_t>(wire_len) + 2 * need<uint64_t>(nseg) + need<uint64_t>(max_frags) +
+                                need<uint32_t>(max_frags) + need<uint64_t>(8 * nseg) + need<uint64_t>(4))};
+    const auto w = c.take<uint8_t>(wire_len);
+    if (wire_len) std::memcpy(w.host, wire, wire_len);
+    const auto so = c.take<uint64_t>(nseg);
+    const auto sl = c.take<uint64_t>(nseg);
+    for (size_t i = 0; i < nseg; ++i) {
+        so.host[i] = segments[i].off;
+        sl.host[i] = segments[i].len;
+    }
+    const size_t start_at = c.off;
+    const auto start = c.take<uint64_t>(max_frags);
+    const size_t len_at = c.off;
+    const auto len = c.take<uint32_t>(max_frags);
+    const auto rows = c.take<uint64_t>(8 * nseg);
+    const auto fres = c.take<uint64_t>(4);
+    codec.check(onc_frame_fragment_streams(codec.get(), w.dev, so.dev, sl.dev, nseg, start.dev, len.dev, nullptr,
+                                           max_frags, rows.dev, fres.dev),
+                "onc_frame_fragment_streams");
+    codec.sync();
+    size_t cap = 0;                  // a reassembled record is never longer than its fragments
+    for (size_t i = 0; i < nseg; ++i) {
+        const uint64_t* q = rows.host + 8 * i;
+        cap += size_t(q[2]);
+        if (per_segment)
+            (*per_segment)[i] = SegmentRecords{q[6], q[7], q[2], int32_t(q[3]), uint32_t(q[4]), uint32_t(q[5])};
+    }
+    const size_t nfrag = size_t(fres.host[0]);
+    r.n_frags = nfrag;
+    if (!nfrag) return r;
+    // the outputs after what is staged (a stage that grows keeps it)
+    const size_t mark = c.off;
+    c.s = codec.stage(mark + need<uint8_t>(cap) + need<uint64_t>(nfrag + 1) + need<int32_t>(nfrag) + need<uint64_t>(6),
+                      mark);
+    const auto out = c.take<uint8_t>(cap);
+    const auto off = c.take<uint64_t>(nfrag + 1);
+    const auto st = c.take<int32_t>(nfrag);
+    const auto res = c.take<uint64_t>(6);
+    codec.check(onc_defragment_extents(codec.get(), c.s.dev, reinterpret_cast<const uint64_t*>(c.s.dev + start_at),
+                                       reinterpret_cast<const uint32_t*>(c.s.dev + len_at), nfrag, out.dev, cap,
+                                       off.dev, st.dev, res.dev),
+                "onc_defragment_extents");
+    codec.sync();
+    uint64_t d[6];
+    std::memcpy(d, res.host, sizeof(d));
+    const size_t n = size_t(d[0]);
+    r.bytes.assign(out.host, out.host + d[2]);
+    r.rec_off.assign(off.host, off.host + n + 1);
+    r.status.assign(st.host, st.host + n);
+    r.n_multi = size_t(d[5]);
+    return r;
+}
+
+inline MixedStreams BatchDecoder::try_from_mixed_streams(Codec& codec, const uint8_t* wire, size_t wire_len,
+                                                         const std::vector<Segment>& segments, DecodeMode mode) {
+    MixedStreams m;
+    const size_t nseg = segments.size();
+    m.per_connection.resize(nseg);
+    std::vector<Decoded> plain = try_from_streams(codec, wire, wire_len, segments, &m.segments, mode);
+    std::vector<Segment> rests;      // of the segments that stopped at a fragmented mark
+    std::vector<size_t> whose;
+    for (size_t i = 0; i < nseg; ++i) {
+        SegmentResult& g = m.segments[i];
+        auto from = plain.begin() + std::ptrdiff_t(g.first);
+        m.per_connection[i].assign(std::make_move_iterator(from), std::make_move_iterator(from + std::ptrdiff_t(g.n)));
+        if (g.status == ONC_ERR_FRAGMENTED) {
+            rests.push_back(Segment{segments[i].off + g.consumed, segments[i].len - g.consumed});
+            whose.push_back(i);
+        }
+    }
+    if (rests.empty()) return m;
+    std::vector<SegmentRecords> per;
+    ReassembledStreams r = reassemble_streams(codec, wire, wire_len, rests, &per);
+    m.reassembled = std::move(r.bytes);          // the views below point into it
+    const size_t n = r.rec_off.size() - 1;
+    std::vector<uint32_t> rec_len(n);
+    for (size_t k = 0; k < n; ++k) rec_len[k] = uint32_t(r.rec_off[k + 1] - r.rec_off[k]);
+    std::vector<Decoded> rebuilt = try_from(codec, m.reassembled.data(), m.reassembled.size(), rec_len, mode);
+    for (size_t j = 0; j < rests.size(); ++j) {
+        SegmentResult& g = m.segments[whose[j]];
+        std::vector<Decoded>& list = m.per_connection[whose[j]];
+        auto from = rebuilt.begin() + std::ptrdiff_t(per[j].first_rec);
+        list.insert(list.end(), std::make_move_iterator(from),
+                    std::make_move_iterator(from + std::ptrdiff_t(per[j].n_rec)));
+        g.n = list.size();
+        g.consumed += per[j].consumed;
+        g.status = per[j].status;
+        g.aux0 = per[j].aux0;
+        g.aux1 = per[j].aux1;
+    }
+    return m;
 }
 
 // The send side: a packed stream of single-fragment records (what

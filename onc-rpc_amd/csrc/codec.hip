@@ -244,9 +244,12 @@ int ensure_defrag(onc_codec* c, uint64_t nfrag) {
 
 // onc_frame_streams' scratch for up to S segments: base (S + 1) and x as
 // u64, cnt, st, two aux words and kStreamKeep kept lengths as u32 — 96 bytes
-// per segment — and a count per write workgroup.
+// per segment — and a count per write workgroup. onc_frame_fragment_streams
+// lays its own state into the same buffer (kernels.h FragStreamsArgs): a third
+// u64 array, a fifth u32 word per segment and two u64 words — 108 bytes per
+// segment — which is what the buffer is sized for.
 uint64_t streams_bytes(uint64_t S) {
-    return 8 * (S + 2) * 2 + 4 * S * (4 + onc::kStreamKeep) + 4 * (onc::streams_write_groups(S) + 4);
+    return 8 * ((S + 2) * 3 + 2) + 4 * S * (5 + onc::kStreamKeep) + 4 * (onc::streams_write_groups(S) + 4);
 }
 int ensure_streams(onc_codec* c, uint64_t nseg) {
     if (nseg <= c->stm_cap) return ONC_RC_OK;
@@ -386,8 +389,8 @@ int onc_codec_reserve(onc_codec* c, uint64_t max_records) {
     // its record lengths, one per fragment at most, fits the scratch above)
     const int rd = ensure_defrag(c, max_records);
     if (rd != ONC_RC_OK) return rd;
-    // onc_frame_streams of up to max_records segments (the scan of their
-    // record counts fits the scratch above)
+    // onc_frame_streams / onc_frame_fragment_streams of up to max_records
+    // segments (the scans of their counts fit the scratch above)
     return ensure_streams(c, max_records);
 }
 
@@ -1029,6 +1032,56 @@ int onc_frame_streams(onc_codec* c, const uint8_t* wire, const uint64_t* seg_off
     return run(c, ONC_K_FRAME_COUNTS, "streams_result", [&] { return onc::launch_streams_result(a, c->stream); });
 }
 
+int onc_frame_fragment_streams(onc_codec* c, const uint8_t* wire, const uint64_t* seg_off, const uint64_t* seg_len,
+                               uint64_t nseg, uint64_t* frag_start, uint32_t* frag_len, uint32_t* frag_seg,
+                               uint64_t max_frags, uint64_t* seg_result, uint64_t* result) {
+    if (!c || !result || nseg > 0xFFFFFFFFull) return ONC_RC_EINVAL;
+    if (nseg && (!seg_off || !seg_len || !seg_result)) return ONC_RC_EINVAL;
+    if (nseg && max_frags && (!wire || !frag_start || !frag_len)) return ONC_RC_EINVAL;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    hipError_t e;
+    if (nseg == 0 || max_frags == 0) {                    // nothing emitted: every row all zeros
+        e = hipMemsetAsync(result, 0, 4 * sizeof(uint64_t), c->stream);
+        if (e == hipSuccess && nseg) e = hipMemsetAsync(seg_result, 0, 8 * nseg * sizeof(uint64_t), c->stream);
+        return e == hipSuccess ? ONC_RC_OK : fail(c, e, "hipMemsetAsync");
+    }
+    int rc = ensure_scratch(c, onc::num_tiles(nseg));
+    if (rc == ONC_RC_OK) rc = ensure_streams(c, nseg);
+    if (rc != ONC_RC_OK) return rc;
+    const uint64_t S = c->stm_cap;
+    onc::FragStreamsArgs a{};
+    a.wire = wire;
+    a.seg_off = seg_off;
+    a.seg_len = seg_len;
+    a.nseg = nseg;
+    a.max_frags = max_frags;
+    a.frag_start = frag_start;
+    a.frag_len = frag_len;
+    a.frag_seg = frag_seg;
+    a.seg_result = seg_result;
+    a.result = result;
+    a.fbase = reinterpret_cast<uint64_t*>(c->stm);
+    a.rbase = a.fbase + (S + 2);
+    a.x = a.rbase + (S + 2);
+    a.cut = a.x + (S + 2);
+    a.fcnt = reinterpret_cast<uint32_t*>(a.cut + 2);
+    a.rcnt = a.fcnt + S;
+    a.st = reinterpret_cast<int32_t*>(a.fcnt + 2 * S);
+    a.aux = a.fcnt + 3 * S;
+    a.keep = a.fcnt + 5 * S;
+    a.blk_stopped = a.keep + onc::kStreamKeep * S;
+    rc = run(c, ONC_K_FRAME, "fragstreams_chase", [&] { return onc::launch_fragstreams_chase(a, c->stream); });
+    // every segment's first fragment and first record index, and their totals
+    // (onc_scan_lengths' launches and timing ids, once each)
+    if (rc == ONC_RC_OK) rc = onc_scan_lengths(c, a.fcnt, nseg, 0, a.fbase);
+    if (rc == ONC_RC_OK) rc = onc_scan_lengths(c, a.rcnt, nseg, 0, a.rbase);
+    if (rc != ONC_RC_OK) return rc;
+    rc = run(c, ONC_K_FRAME_WRITE, "fragstreams_write", [&] { return onc::launch_fragstreams_write(a, c->stream); });
+    if (rc != ONC_RC_OK) return rc;
+    return run(c, ONC_K_FRAME_COUNTS, "fragstreams_result",
+               [&] { return onc::launch_fragstreams_result(a, c->stream); });
+}
+
 // The decode entry points and their bounded forms share one body each:
 // bounded = the wire-length checked kernels (decode.hip kBound, extent.h).
 static int decode_offsets(onc_codec* c, const uint8_t* wire, bool bounded, uint64_t wire_len, const uint64_t* rec_off,
@@ -1304,10 +1357,11 @@ int onc_compact_iov(onc_codec* c, onc_iov_rec* iov, const int32_t* status, uint6
                [&] { return onc::launch_compact_iov_apply(iov, status, n, c->cmp_off, totals, c->stream); });
 }
 
-int onc_defragment(onc_codec* c, const uint8_t* wire, const uint64_t* frag_off, uint64_t nfrag, uint8_t* out,
-                   uint64_t out_cap, uint64_t* rec_off, int32_t* status, uint64_t* result) {
-    if (!c || !rec_off || !result) return ONC_RC_EINVAL;
-    if (nfrag && (!wire || !frag_off || !status || (!out && out_cap))) return ONC_RC_EINVAL;
+// onc_defragment (frag_off) and onc_defragment_extents (frag_start, frag_len)
+// share everything but where a fragment lies; the arguments are checked.
+static int defragment(onc_codec* c, const uint8_t* wire, const uint64_t* frag_off, const uint64_t* frag_start,
+                      const uint32_t* frag_len, uint64_t nfrag, uint8_t* out, uint64_t out_cap, uint64_t* rec_off,
+                      int32_t* status, uint64_t* result) {
     if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
     hipError_t e;
     if (nfrag == 0) {
@@ -1324,6 +1378,8 @@ int onc_defragment(onc_codec* c, const uint8_t* wire, const uint64_t* frag_off, 
     onc::DefragArgs a{};
     a.wire = wire;
     a.frag_off = frag_off;
+    a.frag_start = frag_start;
+    a.frag_len = frag_len;
     a.nfrag = nfrag;
     const uintptr_t oa = reinterpret_cast<uintptr_t>(out);
     a.out = reinterpret_cast<uint8_t*>(oa & ~uintptr_t(15));
@@ -1338,11 +1394,7 @@ int onc_defragment(onc_codec* c, const uint8_t* wire, const uint64_t* frag_off, 
     a.blk = reinterpret_cast<onc::DefragAgg*>(a.S + (F + 2));
     a.info = reinterpret_cast<uint64_t*>(a.blk + defrag_blocks(F) + 1);
     a.M = reinterpret_cast<uint32_t*>(a.info + 2);
-    a.lens = c->lens;
-    // lengths past the last record scan as 0 (how many records there are is
-    // known on the device only)
-    e = hipMemsetAsync(c->lens, 0, nfrag * sizeof(uint32_t), c->stream);
-    if (e != hipSuccess) return fail(c, e, "hipMemsetAsync");
+    a.lens = c->lens;           // (zeroed by defrag_blk: lengths past the last record scan as 0)
     rc = run(c, ONC_K_DEFRAG_PLAN, "defrag_blk", [&] { return onc::launch_defrag_blk(a, c->stream); });
     if (rc == ONC_RC_OK)
         rc = run(c, ONC_K_DEFRAG_PLAN, "defrag_blkscan", [&] { return onc::launch_defrag_blkscan(a, c->stream); });
@@ -1353,6 +1405,21 @@ int onc_defragment(onc_codec* c, const uint8_t* wire, const uint64_t* frag_off, 
         rc = run(c, ONC_K_DEFRAG_PLAN, "defrag_place", [&] { return onc::launch_defrag_place(a, c->stream); });
     if (rc != ONC_RC_OK || out_cap == 0) return rc;
     return run(c, ONC_K_DEFRAG_COPY, "defrag_copy", [&] { return onc::launch_defrag_copy(a, c->stream); });
+}
+
+int onc_defragment(onc_codec* c, const uint8_t* wire, const uint64_t* frag_off, uint64_t nfrag, uint8_t* out,
+                   uint64_t out_cap, uint64_t* rec_off, int32_t* status, uint64_t* result) {
+    if (!c || !rec_off || !result) return ONC_RC_EINVAL;
+    if (nfrag && (!wire || !frag_off || !status || (!out && out_cap))) return ONC_RC_EINVAL;
+    return defragment(c, wire, frag_off, nullptr, nullptr, nfrag, out, out_cap, rec_off, status, result);
+}
+
+int onc_defragment_extents(onc_codec* c, const uint8_t* wire, const uint64_t* frag_start, const uint32_t* frag_len,
+                           uint64_t nfrag, uint8_t* out, uint64_t out_cap, uint64_t* rec_off, int32_t* status,
+                           uint64_t* result) {
+    if (!c || !rec_off || !result) return ONC_RC_EINVAL;
+    if (nfrag && (!wire || !frag_start || !frag_len || !status || (!out && out_cap))) return ONC_RC_EINVAL;
+    return defragment(c, wire, nullptr, frag_start, frag_len, nfrag, out, out_cap, rec_off, status, result);
 }
 
 int onc_fragment(onc_codec* c, const uint8_t* wire, const uint64_t* rec_off, uint64_t n, uint32_t max_frag,

@@ -12,7 +12,7 @@
 //
 //   defrag_blk      per 256 fragments: the plan state of the block as a run
 //                   (defrag_plan.h DefragAgg: records closed, open record's
-//                   fragments and body bytes)
+//                   fragments and body bytes); zeroes the record lengths
 //   defrag_blkscan  one workgroup: exclusive scan of the block states
 //   defrag_frag     per fragment: the state before it = its record index,
 //                   the body bytes before it in its record, first-of-record;
@@ -32,6 +32,11 @@
 //                   when the chunk lies inside one fragment's bytes, byte by
 //                   byte at seams, at the synthesised marks and at the ends
 //                   (compact.hip compact_gather is the precedent).
+//
+// onc_defragment_extents runs the same kernels on fragments that are not back
+// to back (frag_start / frag_len instead of frag_off): defrag_blk, defrag_frag
+// and defrag_place have an extents form (kExt); the copy works from absolute
+// sources and has one form.
 #include "common.h"
 #include "defrag_plan.h"
 #include "kernels.h"
@@ -85,18 +90,33 @@ struct FragElem {
     bool last;
 };
 // Fragment j (< nfrag): its mark is read only for bit 31 (the first byte).
+// kExt: the extents form (onc_defragment_extents) — fragment j lies at
+// frag_start[j] and is frag_len[j] bytes long, its mark included; only this
+// and defrag_place look at where the fragments are.
+template <bool kExt>
 __device__ __forceinline__ FragElem frag_elem(const DefragArgs& a, uint64_t j) {
-    const uint64_t lo = a.frag_off[j], hi = a.frag_off[j + 1];
-    return FragElem{defrag_body(lo, hi), (a.wire[lo] & 0x80u) != 0};
+    if constexpr (kExt) {
+        const uint64_t lo = a.frag_start[j];
+        return FragElem{defrag_body(0, a.frag_len[j]), (a.wire[lo] & 0x80u) != 0};
+    } else {
+        const uint64_t lo = a.frag_off[j], hi = a.frag_off[j + 1];
+        return FragElem{defrag_body(lo, hi), (a.wire[lo] & 0x80u) != 0};
+    }
 }
 
+template <bool kExt>
 __global__ __launch_bounds__(kDfThreads) void defrag_blk_kernel(DefragArgs a) {
     __shared__ DefragAgg s_wave[kDfThreads / 64];
     const uint64_t j = uint64_t(blockIdx.x) * kDfThreads + threadIdx.x;
     DefragAgg v = defrag_none();
     if (j < a.nfrag) {
-        const FragElem f = frag_elem(a, j);
+        const FragElem f = frag_elem<kExt>(a, j);
         v = defrag_elem(f.body, f.last);
+        // lengths past the last record scan as 0 (how many records there are
+        // is known on the device only; defrag_frag sets the records'). Zeroed
+        // here and not by a memset on the stream: every step of the call is a
+        // kernel launch, so a captured call is a chain of kernel nodes.
+        a.lens[j] = 0;
     }
     DefragAgg total;
     block_excl_agg(v, s_wave, &total);
@@ -125,13 +145,14 @@ __global__ __launch_bounds__(kDfThreads) void defrag_blkscan_kernel(DefragArgs a
 // Between this kernel and defrag_place the per-fragment arrays hold the plan:
 // E = body bytes before the fragment in its record, S = its record index,
 // M = 1 for the first fragment of a record.
+template <bool kExt>
 __global__ __launch_bounds__(kDfThreads) void defrag_frag_kernel(DefragArgs a) {
     __shared__ DefragAgg s_wave[kDfThreads / 64];
     const uint64_t j = uint64_t(blockIdx.x) * kDfThreads + threadIdx.x;
     DefragAgg v = defrag_none();
     FragElem f{0, false};
     if (j < a.nfrag) {
-        f = frag_elem(a, j);
+        f = frag_elem<kExt>(a, j);
         v = defrag_elem(f.body, f.last);
     }
     DefragAgg total;
@@ -154,6 +175,9 @@ __global__ __launch_bounds__(kDfThreads) void defrag_frag_kernel(DefragArgs a) {
 // Thread i: record i (rec_off, status), fragment i (its placement), and for
 // i == 0 the result. off = the scan of the record lengths over nfrag entries
 // (zero past the last record, so off[nfrag] = the bytes the batch needs).
+// kExt: result[1] counts the fragments consumed (there is no stream offset
+// to give).
+template <bool kExt>
 __global__ __launch_bounds__(kDfThreads) void defrag_place_kernel(DefragArgs a) {
     const uint64_t i = uint64_t(blockIdx.x) * kDfThreads + threadIdx.x;
     if (i > a.nfrag) return;
@@ -189,14 +213,14 @@ __global__ __launch_bounds__(kDfThreads) void defrag_place_kernel(DefragArgs a) 
         // bytes stand where the synthesised mark goes (S = the mark); a
         // continuation's extent is its body
         a.E[i] = a.origin + e;
-        a.S[i] = a.frag_off[i] + (first ? 0 : 4);
+        a.S[i] = (kExt ? a.frag_start[i] : a.frag_off[i]) + (first ? 0 : 4);
         a.M[i] = mark;
     } else {
         a.E[i] = a.origin + need;
     }
     if (i == 0) {
         a.result[0] = nrec;
-        a.result[1] = a.frag_off[a.nfrag - all.cnt];
+        a.result[1] = kExt ? a.nfrag - all.cnt : a.frag_off[a.nfrag - all.cnt];
         a.result[2] = need;
         a.result[3] = all.cnt;
         a.result[4] = all.tail;
@@ -323,7 +347,8 @@ __global__ __launch_bounds__(kDfThreads) void defrag_copy_kernel(DefragArgs a) {
 static uint32_t df_blocks(uint64_t n) { return uint32_t((n + kDfThreads - 1) / kDfThreads); }
 
 hipError_t launch_defrag_blk(const DefragArgs& a, hipStream_t s) {
-    ONC_LAUNCH(defrag_blk_kernel, dim3(df_blocks(a.nfrag)), dim3(kDfThreads), 0, s, a);
+    if (a.frag_start) ONC_LAUNCH(defrag_blk_kernel<true>, dim3(df_blocks(a.nfrag)), dim3(kDfThreads), 0, s, a);
+    else ONC_LAUNCH(defrag_blk_kernel<false>, dim3(df_blocks(a.nfrag)), dim3(kDfThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -333,12 +358,14 @@ hipError_t launch_defrag_blkscan(const DefragArgs& a, hipStream_t s) {
 }
 
 hipError_t launch_defrag_frag(const DefragArgs& a, hipStream_t s) {
-    ONC_LAUNCH(defrag_frag_kernel, dim3(df_blocks(a.nfrag)), dim3(kDfThreads), 0, s, a);
+    if (a.frag_start) ONC_LAUNCH(defrag_frag_kernel<true>, dim3(df_blocks(a.nfrag)), dim3(kDfThreads), 0, s, a);
+    else ONC_LAUNCH(defrag_frag_kernel<false>, dim3(df_blocks(a.nfrag)), dim3(kDfThreads), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_defrag_place(const DefragArgs& a, hipStream_t s) {
-    ONC_LAUNCH(defrag_place_kernel, dim3(df_blocks(a.nfrag + 1)), dim3(kDfThreads), 0, s, a);
+    if (a.frag_start) ONC_LAUNCH(defrag_place_kernel<true>, dim3(df_blocks(a.nfrag + 1)), dim3(kDfThreads), 0, s, a);
+    else ONC_LAUNCH(defrag_place_kernel<false>, dim3(df_blocks(a.nfrag + 1)), dim3(kDfThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -147,6 +147,11 @@ struct DefragArgs {
     uint64_t* off;          // nfrag + 1: their scan
     DefragAgg* blk;         // per 256 fragments (+ 1: the whole batch)
     uint64_t* info;         // [0] n_multi, [1] start of the first record beyond the capacity
+    // onc_defragment_extents (appended: the fields above keep their kernarg
+    // offsets): fragment j is wire[frag_start[j], frag_start[j] + frag_len[j])
+    // and frag_off is not read (the defrag_* kernels' extents form)
+    const uint64_t* frag_start; // nfrag
+    const uint32_t* frag_len;   // nfrag
 };
 
 // onc_fragment (fragment.hip). Scratch per record: E (8 bytes) and the block
@@ -244,6 +249,33 @@ struct StreamsArgs {
     uint32_t* keep;             // kStreamKeep per segment: its first records' lengths
     uint32_t* blk_stopped;      // per streams_write workgroup: its segments that stopped
 };
+// onc_frame_fragment_streams (streams.hip). Scratch per segment: fbase, rbase
+// and x (8 bytes each), fcnt, rcnt, st and two aux words (4 each), kStreamKeep
+// marks (4 each): 108 bytes; 4 per write workgroup (kStreamKeep segments) and
+// two words for the segment the capacity cuts.
+struct FragStreamsArgs {
+    const uint8_t* wire;
+    const uint64_t* seg_off;    // nseg
+    const uint64_t* seg_len;    // nseg
+    uint64_t nseg;
+    uint64_t max_frags;
+    uint64_t* frag_start;       // max_frags
+    uint32_t* frag_len;         // max_frags
+    uint32_t* frag_seg;         // max_frags, optional
+    uint64_t* seg_result;       // 8 * nseg
+    uint64_t* result;           // [4] fragments emitted, needed, records emitted, segments stopped
+    // per segment, the unbounded chase (max_frags does not enter it)
+    uint64_t* fbase;            // nseg + 1: exclusive scan of fcnt; fbase[nseg] = needed
+    uint64_t* rbase;            // nseg + 1: exclusive scan of rcnt
+    uint64_t* x;                // the end of the last complete record, relative to the segment
+    uint32_t* fcnt;             // fragments of the segment's complete records
+    uint32_t* rcnt;             // its complete records
+    int32_t* st;                // why the walk stops (ONC_OK: at the segment's end)
+    uint32_t* aux;              // 2 per segment
+    uint32_t* keep;             // kStreamKeep per segment: its first marks (the words: bit 31 says last)
+    uint32_t* blk_stopped;      // per fragstreams_write workgroup: its segments that stopped
+    uint64_t* cut;              // [2] fragments and records emitted up to and with the segment the capacity cuts
+};
 // the line policy when at least this many of a sampled workgroup's 64
 // records needed a second first-round window under the standard one
 constexpr uint32_t kLine1Min = 24;
@@ -290,6 +322,7 @@ hipError_t launch_compact_iov_lens(const onc_iov_rec* iov, const int32_t* status
 hipError_t launch_compact_iov_apply(onc_iov_rec* iov, const int32_t* status, uint64_t n, const uint64_t* new_off,
                                     uint64_t* totals, hipStream_t s);
 // defrag.hip
+// (blk, frag, place: the extents form when a.frag_start is set)
 hipError_t launch_defrag_blk(const DefragArgs& a, hipStream_t s);
 hipError_t launch_defrag_blkscan(const DefragArgs& a, hipStream_t s);
 hipError_t launch_defrag_frag(const DefragArgs& a, hipStream_t s);
@@ -310,6 +343,9 @@ hipError_t launch_streams_chase(const StreamsArgs& a, hipStream_t s);
 hipError_t launch_streams_write(const StreamsArgs& a, hipStream_t s);
 hipError_t launch_streams_result(const StreamsArgs& a, hipStream_t s);
 uint64_t streams_write_groups(uint64_t nseg);
+hipError_t launch_fragstreams_chase(const FragStreamsArgs& a, hipStream_t s);
+hipError_t launch_fragstreams_write(const FragStreamsArgs& a, hipStream_t s);
+hipError_t launch_fragstreams_result(const FragStreamsArgs& a, hipStream_t s);
 // decode.hip
 hipError_t launch_decode(const DecArgs& a, int mode, hipStream_t s);
 hipError_t launch_dlen_tiles(const uint32_t* rec_len, uint64_t n, uint64_t* tile_sum, uint64_t* blk_sum, hipStream_t s);

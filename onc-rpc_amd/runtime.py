@@ -43,6 +43,7 @@ EXPORTED = [
     "onc_frame_fragments", "onc_defragment",
     "onc_frame_streams", "onc_decode_extents",
     "onc_fragment", "onc_fragment_iov",
+    "onc_frame_fragment_streams", "onc_defragment_extents",
 ]
 
 # onc_codec_options (include/onc_rpc.h)
@@ -128,6 +129,8 @@ def load_library(path=LIB_PATH):
     lib.onc_fragment.argtypes = [vp, vp, vp, u64, C.c_uint32, vp, u64, vp, vp, vp]
     lib.onc_fragment_iov.argtypes = [vp, vp, u64, C.c_uint32, vp, vp, u64, vp, u64, vp, vp, vp, vp]
     lib.onc_decode_extents.argtypes = [vp, vp, u64, vp, vp, u64, i32, C.POINTER(OncDecoded)]
+    lib.onc_frame_fragment_streams.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp]
+    lib.onc_defragment_extents.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, vp, vp]
     for name in EXPORTED:
         getattr(lib, name).restype = getattr(lib, name).restype or i32
     # a stale library would read a differently laid out onc_batch and label
@@ -356,6 +359,26 @@ class Codec:
         self._check(self.lib.onc_frame_streams(self.h, _ptr(wire), _ptr(seg_off), _ptr(seg_len), nseg,
                                                _ptr(rec_start), _ptr(rec_len), _ptr(rec_seg), max_records,
                                                _ptr(seg_result), _ptr(result)), "onc_frame_streams")
+
+    def frame_fragment_streams(self, wire, seg_off, seg_len, nseg, frag_start, frag_len, frag_seg, max_frags,
+                               seg_result, result):
+        """onc_frame_fragment_streams: frame_streams at fragment level — the
+        fragments of every segment's complete records as extents (frag_seg
+        may be None); seg_result = 8 words per segment, result = 4 words."""
+        self._check(self.lib.onc_frame_fragment_streams(self.h, _ptr(wire), _ptr(seg_off), _ptr(seg_len), nseg,
+                                                        _ptr(frag_start), _ptr(frag_len), _ptr(frag_seg), max_frags,
+                                                        _ptr(seg_result), _ptr(result)),
+                    "onc_frame_fragment_streams")
+
+    def defragment_extents(self, wire, frag_start, frag_len, nfrag, out, rec_off, status, result, out_cap=None):
+        """onc_defragment_extents: defragment of the fragments
+        wire[frag_start[j], +frag_len[j]) (`out`: a tensor or an int device
+        pointer with out_cap); result = 6 words, result[1] counts fragments."""
+        cap = out.numel() if out_cap is None else out_cap
+        optr = C.c_void_p(out) if isinstance(out, int) else _ptr(out)
+        self._check(self.lib.onc_defragment_extents(self.h, _ptr(wire), _ptr(frag_start), _ptr(frag_len), nfrag, optr,
+                                                    cap, _ptr(rec_off), _ptr(status), _ptr(result)),
+                    "onc_defragment_extents")
 
     # -- decode -----------------------------------------------------------
     def decode_extents(self, wire, wire_len, rec_start, rec_len, n, mode, msgs, unix, status, aux0, aux1):
@@ -632,6 +655,73 @@ def frame_host_streams(codec: Codec, slab, seg_off, seg_len, max_records=None, d
     return (start.cpu().numpy().view(np.uint64)[:n].copy(), rlen.cpu().numpy().view(np.uint32)[:n].copy(),
             rseg.cpu().numpy().view(np.uint32)[:n].copy() if with_seg else None,
             rows.cpu().numpy().view(np.uint64)[:6 * nseg].reshape(nseg, 6).copy(), r)
+
+
+def frame_host_fragment_streams(codec: Codec, slab, seg_off, seg_len, max_frags=None, device="cuda", with_seg=True):
+    """Convenience: a host slab and its segments -> onc_frame_fragment_streams
+    -> (frag_start[n], frag_len[n], frag_seg[n] or None, seg_result[nseg, 8],
+    result[4]) on the host. max_frags None: room for every mark the segments
+    can hold."""
+    torch = _torch()
+    w = to_device(np.frombuffer(bytes(slab) + b"\0" * 16, np.uint8), device)
+    so = np.ascontiguousarray(seg_off, np.uint64)
+    sl = np.ascontiguousarray(seg_len, np.uint64)
+    nseg = len(so)
+    m = int(sl.sum()) // 4 + 1 if max_frags is None else max_frags
+    d_so = torch.from_numpy(np.append(so, np.uint64(0)).view(np.int64).copy()).to(device)
+    d_sl = torch.from_numpy(np.append(sl, np.uint64(0)).view(np.int64).copy()).to(device)
+    start = torch.full((m + 1,), -1, dtype=torch.int64, device=device)
+    flen = torch.full((m + 1,), -1, dtype=torch.int32, device=device)
+    fseg = torch.full((m + 1,), -1, dtype=torch.int32, device=device) if with_seg else None
+    rows = torch.full((8 * nseg + 1,), -1, dtype=torch.int64, device=device)
+    res = torch.full((4,), -1, dtype=torch.int64, device=device)
+    codec.frame_fragment_streams(w, d_so, d_sl, nseg, start, flen, fseg, m, rows, res)
+    codec.sync()
+    r = res.cpu().numpy().view(np.uint64).copy()
+    n = int(r[0])
+    return (start.cpu().numpy().view(np.uint64)[:n].copy(), flen.cpu().numpy().view(np.uint32)[:n].copy(),
+            fseg.cpu().numpy().view(np.uint32)[:n].copy() if with_seg else None,
+            rows.cpu().numpy().view(np.uint64)[:8 * nseg].reshape(nseg, 8).copy(), r)
+
+
+def defragment_host_extents(codec: Codec, wire, frag_start, frag_len, out_cap=None, shift=0, device="cuda"):
+    """Convenience: host wire bytes and fragment extents ->
+    onc_defragment_extents -> (the out_cap bytes from `out` on (out_cap None:
+    the bytes the batch needs), rec_off[n+1], status[n], result[6]) on the
+    host. `out` starts `shift` bytes past a 16-byte aligned address and is
+    zero-filled before the call."""
+    torch = _torch()
+    fs = np.ascontiguousarray(frag_start, np.uint64)
+    fl = np.ascontiguousarray(frag_len, np.uint32)
+    nfrag = len(fs)
+    w = to_device(np.frombuffer(bytes(wire) + b"\0" * 16, np.uint8), device)
+    d_fs = torch.from_numpy(np.append(fs, np.uint64(0)).view(np.int64).copy()).to(device)
+    d_fl = torch.from_numpy(np.append(fl, np.uint32(0)).view(np.int32).copy()).to(device)
+    cap = int(fl.sum()) if out_cap is None else out_cap      # a reassembled record is never longer than its fragments
+    base = torch.zeros(16 + shift + cap + 16, dtype=torch.uint8, device=device)
+    lo = (-base.data_ptr()) % 16 + shift
+    rec_off = torch.zeros(nfrag + 1, dtype=torch.int64, device=device)
+    status = torch.zeros(max(nfrag, 1), dtype=torch.int32, device=device)
+    res = torch.zeros(6, dtype=torch.int64, device=device)
+    codec.defragment_extents(w, d_fs, d_fl, nfrag, base.data_ptr() + lo, rec_off, status, res, out_cap=cap)
+    codec.sync()
+    r = res.cpu().numpy().view(np.uint64).copy()
+    n = int(r[0])
+    size = min(int(r[2]), cap) if out_cap is None else cap
+    return (base.cpu().numpy()[lo:lo + size].tobytes(), rec_off.cpu().numpy().view(np.uint64)[:n + 1].copy(),
+            status.cpu().numpy()[:n].copy(), r)
+
+
+def reassemble_host_streams(codec: Codec, slab, seg_off, seg_len, device="cuda"):
+    """Convenience: a host slab and its segments -> onc_frame_fragment_streams
+    + onc_defragment_extents -> (reassembled bytes, rec_off[n+1], status[n],
+    seg_result[nseg, 8], framing result[4], defragment result[6]) on the host.
+    The reassembled bytes are a packed stream of single-fragment records:
+    records [first_rec, first_rec + n_rec) of it are segment s's."""
+    start, flen, _, rows, fres = frame_host_fragment_streams(codec, slab, seg_off, seg_len, device=device,
+                                                              with_seg=False)
+    out, rec_off, status, res = defragment_host_extents(codec, slab, start, flen, device=device)
+    return out, rec_off, status, rows, fres, res
 
 
 def decode_host_extents(codec: Codec, wire: np.ndarray, rec_start, rec_len, mode, wire_len=None, device="cuda"):
