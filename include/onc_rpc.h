@@ -83,7 +83,11 @@ extern "C" {
  *    on the send side), which reuses the existing status codes and
  *    onc_defragment's timing ids; onc_frame_fragment_streams and
  *    onc_defragment_extents (fragmented records of many connections
- *    reassembled in one call), which add no status code and no timing id. */
+ *    reassembled in one call), which add no status code and no timing id;
+ *    onc_defragment_heads and onc_decode_heads (fragmented records decoded
+ *    without copying their payloads), which add no status code and no timing
+ *    id: the one new outcome is a reason of ONC_DEC_BAD_EXTENT,
+ *    ONC_EXTENT_HEAD_SHORT. */
 #define ONC_RPC_ABI_VERSION 8
 
 /* ------------------------------------------------------------------------ */
@@ -224,6 +228,15 @@ extern "C" {
 #define ONC_EXTENT_START_PAST_WIRE 1 /* the record starts past wire_len */
 #define ONC_EXTENT_END_PAST_WIRE   2 /* the record ends past wire_len */
 #define ONC_EXTENT_NOT_MONOTONIC   3 /* rec_off[i+1] < rec_off[i] (offset forms) */
+#define ONC_EXTENT_HEAD_SHORT      4 /* onc_decode_heads: the record's header does not fit its head */
+/* The furthest the message parse reaches into a record (slice mode, the
+ * longer one): 4 for the mark, 24 for xid, message type and the four Call
+ * words, and two auths of 8 (flavor, length) + 4 + 4 (stamp, name length) +
+ * 256 (name) + 12 (uid, gid, gid count) + 64 (gids) each — unix_params.rs:
+ * 96-113 reads the block before its length is compared, and flavor.rs:83
+ * bounds only the declared length. A head of ONC_HEAD_SPAN_MAX rounded up to
+ * 16 (736) holds every header. */
+#define ONC_HEAD_SPAN_MAX 724
 
 /* Batch-level return codes of the API functions */
 #define ONC_RC_OK        0
@@ -500,7 +513,11 @@ int onc_abi_version(void);
  * counts, record counts) under onc_scan_lengths' ids, its write pass
  * (fragstreams_write) under ONC_K_FRAME_WRITE and its result
  * (fragstreams_result) under ONC_K_FRAME_COUNTS. onc_defragment_extents
- * reports as onc_defragment does (ONC_K_DEFRAG_PLAN / ONC_K_DEFRAG_COPY). */
+ * reports as onc_defragment does (ONC_K_DEFRAG_PLAN / ONC_K_DEFRAG_COPY).
+ * onc_defragment_heads reports its plan launches (defrag_blk, defrag_blkscan,
+ * defrag_frag, heads_place) under ONC_K_DEFRAG_PLAN and its gather
+ * (heads_gather) under ONC_K_DEFRAG_COPY; it launches no onc_scan_lengths
+ * kernel. onc_decode_heads reports under ONC_K_DEC_PARSE. */
 #define ONC_K_ENC_LEN      0
 #define ONC_K_SCAN_TILES   1
 #define ONC_K_ENC_EMIT     2
@@ -943,6 +960,72 @@ int onc_defragment_extents(onc_codec* codec, const uint8_t* wire,
                            uint64_t* rec_off /*[dev, nfrag + 1]*/, int32_t* status /*[dev, nfrag]*/,
                            uint64_t* result /*[dev, 6]*/);
 
+/* The heads of fragmented records: what a decoder needs from a reassembled
+ * record — its synthesised mark and its first bytes, contiguous, and its
+ * true length — without moving a payload byte (the receive-side counterpart
+ * of onc_fragment_iov; the reference's decode borrows the payload,
+ * call_body.rs:53-59). The fragments are onc_defragment_extents': fragment j
+ * is wire[frag_start[j], frag_start[j] + frag_len[j]), mark included,
+ * frag_len >= 4, in any address order, overlaps allowed; the extents are
+ * trusted and the mark is read only for bit 31. Record r's head goes to the
+ * fixed-stride slot heads + r * head_len; the rest of the record stays where
+ * it arrived and is located by rec_frag / frag_pre. The result is exactly
+ * that of this loop:
+ *
+ *   r = first = 0; B = 0; multi = 0
+ *   for j in 0 .. nfrag-1:
+ *       frag_pre[j] = B                          # body bytes of its record before fragment j (pending fragments too)
+ *       B += frag_len[j] - 4
+ *       if wire[frag_start[j]] & 0x80:           # last fragment: record r = fragments [first, j]
+ *           rec_frag[r] = first
+ *           if B >= 2^31: rec_len[r] = 0; status[r] = ONC_ENC_TOO_LONG
+ *           else:
+ *               rec_len[r] = 4 + B
+ *               status[r] = r < max_records ? ONC_OK : ONC_ENC_WRITE_ZERO
+ *               if OK: slot = heads + r * head_len
+ *                      slot[0, 4) = BE32(0x80000000 | B)
+ *                      slot[4, min(4 + B, head_len)) = the first bytes of the bodies of fragments first..j, concatenated
+ *           multi += (j > first); r++; first = j + 1; B = 0
+ *   rec_frag[r] = first
+ *   result = {r, first, r * head_len, nfrag - first, B, multi}
+ *
+ * Agreement with the packed form: slot r holds byte for byte the first
+ * min(rec_len[r], head_len) bytes of record r in onc_defragment_extents'
+ * output, rec_len[r] is rec_off[r+1] - rec_off[r] there, and result[0, 1, 3,
+ * 4, 5] are that call's; result[2] is the heads capacity, in bytes, that the
+ * batch needs. Nothing is written in a slot past min(rec_len[r], head_len),
+ * in the slot of a record that is not OK, in heads at or past max_records *
+ * head_len, in rec_len / status from r on, or in rec_frag past r.
+ * head_len is a multiple of 16 in [64, 4096], else ONC_RC_EINVAL; heads must
+ * be 16-byte aligned, else ONC_RC_EALIGN. NULL codec, rec_frag or result is
+ * ONC_RC_EINVAL whatever nfrag is; with nfrag > 0 so is a NULL wire,
+ * frag_start, frag_len, rec_len, frag_pre or status; NULL heads with
+ * max_records > 0 is ONC_RC_EINVAL. nfrag == 0 gives rec_frag[0] = 0 and a
+ * zero result and needs nothing else.
+ * Reads: only the whole aligned 16-byte granules of the wire that hold a
+ * mark or one of the head bytes copied; no byte of a record at body position
+ * >= head_len - 4 is read, so framing-only extents over a mapped host slab
+ * stay cheap.
+ * Locating the payload: record byte p >= 4 of record r is body byte p - 4; it
+ * lies in the last fragment j in [rec_frag[r], rec_frag[r+1]) with
+ * frag_pre[j] <= p - 4, at wire[frag_start[j] + 4 + (p - 4 - frag_pre[j])] —
+ * no piece list is needed.
+ * Asynchronous on the codec's stream; every step is a kernel launch (no
+ * memset), so a captured call is a chain of kernel nodes. Scratch is
+ * onc_defragment's buffer, no more than 32 bytes per fragment, covered by
+ * onc_codec_reserve(max_records >= nfrag); growing it inside a capture is
+ * ONC_RC_ECAPTURE. Timing ids: the plan launches report under
+ * ONC_K_DEFRAG_PLAN, the gather under ONC_K_DEFRAG_COPY. */
+int onc_defragment_heads(onc_codec* codec, const uint8_t* wire,
+                         const uint64_t* frag_start, const uint32_t* frag_len, uint64_t nfrag,
+                         uint32_t head_len,
+                         uint8_t* heads, uint64_t max_records,
+                         uint32_t* rec_len  /*[dev, nfrag]*/,
+                         uint64_t* rec_frag /*[dev, nfrag + 1]*/,
+                         uint64_t* frag_pre /*[dev, nfrag]*/,
+                         int32_t* status    /*[dev, nfrag]*/,
+                         uint64_t* result   /*[dev, 6]*/);
+
 /* The send side of RFC 5531 §11, the exact inverse of onc_defragment: every
  * record of a packed stream cut into fragments of at most max_frag body
  * bytes, as a sender that flushes through a bounded buffer writes them, or
@@ -1177,6 +1260,39 @@ int onc_decode_body_bounded(onc_codec* codec, int root, const uint8_t* wire, uin
 int onc_decode_extents(onc_codec* codec, const uint8_t* wire, uint64_t wire_len,
                        const uint64_t* rec_start, const uint32_t* rec_len, uint64_t n,
                        int mode, const onc_decoded* out);
+
+/* Decode records of which only the head is present (onc_defragment_heads'
+ * output, or the header buffers of a NIC that splits header and data):
+ * record i is a record of rec_len[i] bytes whose first P_i = min(rec_len[i],
+ * head_len) bytes exist, at heads + i * head_len. It is decoded exactly as
+ * onc_decode decodes the whole record: status and aux words, the descriptor,
+ * the AUTH_UNIX slots (grouped per 64 output records from 128g). Every wire
+ * offset in the outputs is relative to heads — i * head_len + the position
+ * in the record: payload_off, the auth refs of the non-UNIX kinds, name_off —
+ * so payload_off - i * head_len is the payload's position in the record;
+ * payload_len is the true length (rec_len[i] minus that position). A decoded
+ * batch re-encodes with auth_arena = heads.
+ * The one new outcome is a record whose header does not fit its head:
+ * ONC_DEC_BAD_EXTENT with aux0 = ONC_EXTENT_HEAD_SHORT and aux1 = 0, a zeroed
+ * descriptor, no slot. (a) The parse proceeds in the reference's order; if it
+ * needs a 4-byte word, or the gid block, that ends past P_i while ending
+ * inside the record, the record is HEAD_SHORT (a read ending past the record
+ * itself is still the reference's short-read error). (b) A parse that ends OK
+ * but whose header — up to where the payload starts, or the whole record when
+ * it has no payload — reaches past P_i is HEAD_SHORT too (a Call's verifier
+ * body is skipped, never read): every auth body and machine name of an OK
+ * record lies inside heads. An error met before any such read is reported
+ * exactly as onc_decode reports it. With head_len >= 736 (ONC_HEAD_SPAN_MAX
+ * rounded up) HEAD_SHORT cannot occur. rec_len[i] == 0 decodes as onc_decode
+ * decodes an empty extent.
+ * head_len is a multiple of 16 in [64, 4096], else ONC_RC_EINVAL; heads must
+ * be 16-byte aligned, else ONC_RC_EALIGN. Reads: only the whole 16-byte
+ * granules of slot i that hold bytes below P_i; the bytes of a slot past P_i,
+ * and the next slot, never affect a result. No scratch; graph capture and
+ * the other return codes as onc_decode_extents; timing under ONC_K_DEC_PARSE;
+ * both first-round policies apply, bounded by P_i. */
+int onc_decode_heads(onc_codec* codec, const uint8_t* heads, uint32_t head_len,
+                     const uint32_t* rec_len, uint64_t n, int mode, const onc_decoded* out);
 
 /* serialised_len() of every descriptor as `root` + the checks of that
  * root's serialise_into: shape (ONC_ENC_BAD_DESCRIPTOR), construction panics

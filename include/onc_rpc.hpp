@@ -768,6 +768,8 @@ struct MixedStreams {
     std::vector<uint8_t> reassembled;
 };
 
+struct FragmentedHeads;   // try_from_fragmented_heads' result (defined with reassemble_heads below)
+
 // ----------------------------------------------------------------------------
 // BatchDecoder: try_from of many records (one buffer per record)
 // ----------------------------------------------------------------------------
@@ -827,6 +829,18 @@ public:
     // onc_frame_fragment_streams + onc_defragment_extents) and decoded.
     MixedStreams try_from_mixed_streams(Codec& codec, const uint8_t* wire, size_t wire_len,
                                         const std::vector<Segment>& segments, DecodeMode mode = DecodeMode::Slice);
+
+    // Fragmenting peers without the copy: every segment's fragment chain
+    // followed (onc_frame_fragment_streams), only each record's head gathered
+    // (onc_defragment_heads) and decoded (onc_decode_heads); the payloads stay
+    // in the caller's wire and come back as slices of it
+    // (FragmentedHeads::payload_pieces). If a record's header does not fit a
+    // head of head_len bytes (ONC_EXTENT_HEAD_SHORT) the batch is done once
+    // more with 736-byte heads, which hold every header: the result is always
+    // the exact one. head_len 160 is the decode window's size.
+    FragmentedHeads try_from_fragmented_heads(Codec& codec, const uint8_t* wire, size_t wire_len,
+                                              const std::vector<Segment>& segments,
+                                              DecodeMode mode = DecodeMode::Slice, uint32_t head_len = 160);
 
 private:
     std::vector<Decoded> streams_at(Codec& codec, const uint8_t* wire, const uint8_t* dev_wire, size_t wire_len,
@@ -1565,6 +1579,203 @@ inline ReassembledStreams reassemble_streams(Codec& codec, const uint8_t* wire, 
     r.status.assign(st.host, st.host + n);
     r.n_multi = size_t(d[5]);
     return r;
+}
+
+// The heads of many connections' fragmented records (reassemble_streams
+// without the payloads): the fragments of every segment's complete records
+// found in one call (onc_frame_fragment_streams) and the first head_len bytes
+// of every record — its synthesised mark included — gathered into fixed-stride
+// slots in one call (onc_defragment_heads). The rest of a record stays in the
+// caller's wire: pieces() lists any range of it as slices of that wire.
+struct ReassembledHeads {
+    uint32_t head_len = 0;
+    std::vector<uint8_t> heads;        // n * head_len: slot r at r * head_len, min(rec_len[r], head_len) bytes of it set
+    std::vector<uint32_t> rec_len;     // n: the records' true lengths (0: ONC_ENC_TOO_LONG)
+    std::vector<int32_t> status;       // n: ONC_OK or ONC_ENC_TOO_LONG
+    std::vector<uint64_t> rec_frag;    // n + 1: record r is fragments [rec_frag[r], rec_frag[r + 1])
+    std::vector<uint64_t> frag_pre;    // per fragment: the body bytes of its record before it
+    std::vector<uint64_t> frag_start;  // per fragment: where it starts in the wire (its mark)
+    std::vector<uint32_t> frag_len;    // per fragment: its length, mark included
+    size_t n_multi = 0;                // records that came in more than one fragment
+    size_t n() const { return rec_len.size(); }
+    size_t n_frags() const { return frag_start.size(); }
+
+    // Record bytes [pos, pos + len) of record r (pos >= 4: past the mark,
+    // pos + len <= rec_len[r]) as slices of `wire`, in order.
+    std::vector<Bytes> pieces(const uint8_t* wire, size_t r, uint64_t pos, uint64_t len) const {
+        std::vector<Bytes> out;
+        if (!len) return out;
+        const uint64_t lo = rec_frag[r], hi = rec_frag[r + 1];
+        uint64_t x = pos - 4, left = len;
+        // the last fragment j in [lo, hi) with frag_pre[j] <= x
+        uint64_t a = lo, b = hi;
+        while (b - a > 1) {
+            const uint64_t mid = a + (b - a) / 2;
+            if (frag_pre[mid] <= x) a = mid;
+            else b = mid;
+        }
+        for (uint64_t j = a; j < hi && left; ++j) {
+            const uint64_t body = frag_len[j] - 4, at = x - frag_pre[j];
+            if (at >= body) continue;                       // an empty fragment
+            const uint64_t take = std::min(left, body - at);
+            out.push_back(Bytes(wire + frag_start[j] + 4 + at, size_t(take)));
+            x += take;
+            left -= take;
+        }
+        return out;
+    }
+};
+
+inline ReassembledHeads reassemble_heads(Codec& codec, const uint8_t* wire, size_t wire_len,
+                                         const std::vector<Segment>& segments, uint32_t head_len = 160,
+                                         std::vector<SegmentRecords>* per_segment = nullptr) {
+    using detail::need;
+    ReassembledHeads r;
+    r.head_len = head_len;
+    r.rec_frag.assign(1, 0);
+    const size_t nseg = segments.size();
+    if (per_segment) per_segment->assign(nseg, SegmentRecords{});
+    if (head_len < 64 || head_len > 4096 || head_len % 16) throw CodecError("reassemble_heads: head_len");
+    if (!nseg) return r;
+    size_t max_frags = 1;
+    for (const Segment& g : segments) {
+        if (g.off > wire_len || g.len > wire_len - g.off) throw CodecError("reassemble_heads: segment outside the wire");
+        max_frags += size_t(g.len / 4);
+    }
+    detail::Carve c{codec.stage(need<uint8_t>(wire_len) + 2 * need<uint64_t>(nseg) + need<uint64_t>(max_frags) +
+                                need<uint32_t>(max_frags) + need<uint64_t>(8 * nseg) + need<uint64_t>(4))};
+    const auto w = c.take<uint8_t>(wire_len);
+    if (wire_len) std::memcpy(w.host, wire, wire_len);
+    const auto so = c.take<uint64_t>(nseg);
+    const auto sl = c.take<uint64_t>(nseg);
+    for (size_t i = 0; i < nseg; ++i) {
+        so.host[i] = segments[i].off;
+        sl.host[i] = segments[i].len;
+    }
+    const size_t start_at = c.off;
+    const auto start = c.take<uint64_t>(max_frags);
+    const size_t len_at = c.off;
+    const auto len = c.take<uint32_t>(max_frags);
+    const auto rows = c.take<uint64_t>(8 * nseg);
+    const auto fres = c.take<uint64_t>(4);
+    codec.check(onc_frame_fragment_streams(codec.get(), w.dev, so.dev, sl.dev, nseg, start.dev, len.dev, nullptr,
+                                           max_frags, rows.dev, fres.dev),
+                "onc_frame_fragment_streams");
+    codec.sync();
+    if (per_segment)
+        for (size_t i = 0; i < nseg; ++i) {
+            const uint64_t* q = rows.host + 8 * i;
+            (*per_segment)[i] = SegmentRecords{q[6], q[7], q[2], int32_t(q[3]), uint32_t(q[4]), uint32_t(q[5])};
+        }
+    const size_t nfrag = size_t(fres.host[0]);
+    const size_t nrec = size_t(fres.host[2]);
+    if (!nfrag) return r;
+    r.frag_start.assign(start.host, start.host + nfrag);
+    r.frag_len.assign(len.host, len.host + nfrag);
+    // the outputs after what is staged (a stage that grows keeps it)
+    const size_t mark = c.off;
+    c.s = codec.stage(mark + need<uint8_t>(nrec * head_len) + need<uint32_t>(nfrag) + 2 * need<uint64_t>(nfrag + 1) +
+                          need<int32_t>(nfrag) + need<uint64_t>(6),
+                      mark);
+    const auto heads = c.take<uint8_t>(nrec * head_len);
+    const auto rl = c.take<uint32_t>(nfrag);
+    const auto rf = c.take<uint64_t>(nfrag + 1);
+    const auto fp = c.take<uint64_t>(nfrag + 1);
+    const auto st = c.take<int32_t>(nfrag);
+    const auto res = c.take<uint64_t>(6);
+    std::memset(heads.host, 0, nrec * head_len);            // (slot bytes past a short record stay zero)
+    codec.check(onc_defragment_heads(codec.get(), c.s.dev, reinterpret_cast<const uint64_t*>(c.s.dev + start_at),
+                                     reinterpret_cast<const uint32_t*>(c.s.dev + len_at), nfrag, head_len, heads.dev,
+                                     nrec, rl.dev, rf.dev, fp.dev, st.dev, res.dev),
+                "onc_defragment_heads");
+    codec.sync();
+    uint64_t d[6];
+    std::memcpy(d, res.host, sizeof(d));
+    const size_t n = size_t(d[0]);
+    if (n != nrec) throw CodecError("reassemble_heads: record counts differ");
+    r.heads.assign(heads.host, heads.host + n * head_len);
+    r.rec_len.assign(rl.host, rl.host + n);
+    r.rec_frag.assign(rf.host, rf.host + n + 1);
+    r.frag_pre.assign(fp.host, fp.host + nfrag);
+    r.status.assign(st.host, st.host + n);
+    r.n_multi = size_t(d[5]);
+    return r;
+}
+
+// What try_from_fragmented_heads returns: the records of all segments in
+// segment order (segment s's are results [first_rec, first_rec + n_rec) of
+// segments[s]). A result's message borrows `heads.heads` for its auth bodies
+// and machine names; its own payload view covers only the payload bytes that
+// lie inside the head. The whole payload is payload_pieces(r) — slices of the
+// caller's wire, nothing copied — or payload(r), a gathered copy.
+struct FragmentedHeads {
+    std::vector<Decoded> results;
+    std::vector<SegmentRecords> segments;
+    ReassembledHeads heads;
+    std::vector<uint64_t> payload_pos;     // per record: where its payload starts in the record (0: none)
+    std::vector<uint64_t> payload_len;     // per record: its true length
+    const uint8_t* wire = nullptr;
+    bool retried = false;                  // a header did not fit head_len: decoded from 736-byte heads
+
+    std::vector<Bytes> payload_pieces(size_t r) const {
+        if (!payload_len[r]) return {};
+        return heads.pieces(wire, r, payload_pos[r], payload_len[r]);
+    }
+    std::vector<uint8_t> payload(size_t r) const {
+        std::vector<uint8_t> out;
+        out.reserve(size_t(payload_len[r]));
+        for (const Bytes& b : payload_pieces(r)) out.insert(out.end(), b.ptr, b.ptr + b.len);
+        return out;
+    }
+};
+
+inline FragmentedHeads BatchDecoder::try_from_fragmented_heads(Codec& codec, const uint8_t* wire, size_t wire_len,
+                                                               const std::vector<Segment>& segments, DecodeMode mode,
+                                                               uint32_t head_len) {
+    using detail::need;
+    constexpr uint32_t kFull = (ONC_HEAD_SPAN_MAX + 15u) & ~15u;    // 736: every header fits
+    FragmentedHeads f;
+    f.wire = wire;
+    for (;;) {
+        f.heads = reassemble_heads(codec, wire, wire_len, segments, head_len, &f.segments);
+        const size_t n = f.heads.n();
+        f.results.clear();
+        f.payload_pos.assign(n, 0);
+        f.payload_len.assign(n, 0);
+        if (!n) return f;
+        detail::Carve c{codec.stage(need<uint8_t>(n * head_len) + need<uint32_t>(n) + out_bytes(n))};
+        const auto h = c.take<uint8_t>(n * head_len);
+        std::memcpy(h.host, f.heads.heads.data(), n * head_len);
+        const auto l = c.take<uint32_t>(n);
+        std::memcpy(l.host, f.heads.rec_len.data(), n * 4);
+        const Out o = take_out(c, n);
+        const onc_decoded d = o.dev();
+        codec.check(onc_decode_heads(codec.get(), h.dev, head_len, l.dev, n, int(mode), &d), "onc_decode_heads");
+        codec.sync();
+        bool head_short = false;
+        for (size_t i = 0; i < n; ++i)
+            head_short = head_short || (o.status.host[i] == ONC_DEC_BAD_EXTENT && o.aux0.host[i] == ONC_EXTENT_HEAD_SHORT);
+        if (head_short && head_len < kFull) {
+            head_len = kFull;
+            f.retried = true;
+            continue;
+        }
+        // the messages' own payload views end with the head
+        for (size_t i = 0; i < n; ++i) {
+            if (o.status.host[i] != ONC_OK) continue;
+            onc_msg& m = o.msgs.host[i];
+            const bool pay = m.msg_type == ONC_MSG_CALL ||
+                             (m.reply_stat == ONC_REPLY_ACCEPTED && m.stat == ONC_ACCEPT_SUCCESS);
+            if (!pay) continue;
+            const uint64_t pos = m.payload_off - uint64_t(i) * head_len;
+            f.payload_pos[i] = pos;
+            f.payload_len[i] = m.payload_len;
+            const uint64_t present = std::min<uint64_t>(f.heads.rec_len[i], head_len);
+            m.payload_len = uint32_t(std::min<uint64_t>(m.payload_len, present > pos ? present - pos : 0));
+        }
+        f.results = results(o, n, f.heads.heads.data());
+        return f;
+    }
 }
 
 inline MixedStreams BatchDecoder::try_from_mixed_streams(Codec& codec, const uint8_t* wire, size_t wire_len,

@@ -1134,6 +1134,26 @@ int onc_decode_extents(onc_codec* c, const uint8_t* wire, uint64_t wire_len, con
     return run(c, ONC_K_DEC_PARSE, "decode", [&] { return onc::launch_decode(a, mode, c->stream); });
 }
 
+int onc_decode_heads(onc_codec* c, const uint8_t* heads, uint32_t head_len, const uint32_t* rec_len, uint64_t n,
+                     int mode, const onc_decoded* out) {
+    if (!c || !out || (mode != ONC_DECODE_SLICE && mode != ONC_DECODE_BYTES)) return ONC_RC_EINVAL;
+    if (!onc::heads_len_ok(head_len)) return ONC_RC_EINVAL;
+    if (reinterpret_cast<uintptr_t>(heads) & 15) return ONC_RC_EALIGN;
+    if (n == 0) return ONC_RC_OK;
+    if (!heads || !rec_len || !out->msgs || !out->unix_params || !out->status || !out->aux0 || !out->aux1)
+        return ONC_RC_EINVAL;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    onc::DecArgs a{};
+    a.n = n;
+    a.wire = heads;
+    a.out = *out;
+    a.variant = c->variant;
+    a.rec_len = rec_len;
+    a.head_len = head_len;
+    decode_policy(c, a);
+    return run(c, ONC_K_DEC_PARSE, "decode", [&] { return onc::launch_decode(a, mode, c->stream); });
+}
+
 static int decode_lengths(onc_codec* c, const uint8_t* wire, bool bounded, uint64_t wire_len, const uint32_t* rec_len,
                           uint64_t n, uint64_t base, int mode, uint64_t* rec_off, const onc_decoded* out) {
     if (!c || !out || (mode != ONC_DECODE_SLICE && mode != ONC_DECODE_BYTES)) return ONC_RC_EINVAL;
@@ -1420,6 +1440,62 @@ int onc_defragment_extents(onc_codec* c, const uint8_t* wire, const uint64_t* fr
     if (!c || !rec_off || !result) return ONC_RC_EINVAL;
     if (nfrag && (!wire || !frag_start || !frag_len || !status || (!out && out_cap))) return ONC_RC_EINVAL;
     return defragment(c, wire, nullptr, frag_start, frag_len, nfrag, out, out_cap, rec_off, status, result);
+}
+
+int onc_defragment_heads(onc_codec* c, const uint8_t* wire, const uint64_t* frag_start, const uint32_t* frag_len,
+                         uint64_t nfrag, uint32_t head_len, uint8_t* heads, uint64_t max_records, uint32_t* rec_len,
+                         uint64_t* rec_frag, uint64_t* frag_pre, int32_t* status, uint64_t* result) {
+    if (!c || !rec_frag || !result || !onc::heads_len_ok(head_len)) return ONC_RC_EINVAL;
+    if (nfrag && (!wire || !frag_start || !frag_len || !rec_len || !frag_pre || !status)) return ONC_RC_EINVAL;
+    if (!heads && max_records) return ONC_RC_EINVAL;
+    if (reinterpret_cast<uintptr_t>(heads) & 15) return ONC_RC_EALIGN;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    onc::HeadsArgs h{};
+    h.wire = wire;
+    h.frag_start = frag_start;
+    h.frag_len = frag_len;
+    h.nfrag = nfrag;
+    h.head_len = head_len;
+    h.heads = heads;
+    h.max_records = max_records;
+    h.rec_len = rec_len;
+    h.rec_frag = rec_frag;
+    h.frag_pre = frag_pre;
+    h.status = status;
+    h.result = result;
+    if (nfrag == 0) return run(c, ONC_K_DEFRAG_PLAN, "heads_empty", [&] { return onc::launch_heads_empty(h, c->stream); });
+    int rc = ensure_lens(c, nfrag);
+    if (rc == ONC_RC_OK) rc = ensure_defrag(c, nfrag);
+    if (rc != ONC_RC_OK) return rc;
+    forget_plan(c);             // (ensure_lens' buffer is the plan's too)
+    // the plan of onc_defragment_extents, its E written where the caller
+    // wants frag_pre; no placement scan (`off` stays unused)
+    const uint64_t F = c->dfr_cap;
+    onc::DefragArgs a{};
+    a.wire = wire;
+    a.frag_start = frag_start;
+    a.frag_len = frag_len;
+    a.nfrag = nfrag;
+    a.E = frag_pre;
+    a.S = reinterpret_cast<uint64_t*>(c->dfr);
+    a.blk = reinterpret_cast<onc::DefragAgg*>(a.S + (F + 2));
+    a.info = reinterpret_cast<uint64_t*>(a.blk + defrag_blocks(F) + 1);
+    a.M = reinterpret_cast<uint32_t*>(a.info + 2);
+    a.lens = c->lens;
+    h.S = a.S;
+    h.M = a.M;
+    h.lens = a.lens;
+    h.blk = a.blk;
+    h.info = a.info;
+    rc = run(c, ONC_K_DEFRAG_PLAN, "defrag_blk", [&] { return onc::launch_defrag_blk(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "defrag_blkscan", [&] { return onc::launch_defrag_blkscan(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "defrag_frag", [&] { return onc::launch_defrag_frag(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "heads_place", [&] { return onc::launch_heads_place(h, c->stream); });
+    if (rc != ONC_RC_OK || max_records == 0) return rc;
+    return run(c, ONC_K_DEFRAG_COPY, "heads_gather", [&] { return onc::launch_heads_gather(h, c->stream); });
 }
 
 int onc_fragment(onc_codec* c, const uint8_t* wire, const uint64_t* rec_off, uint64_t n, uint32_t max_frag,

@@ -83,6 +83,41 @@ struct Rd {
     }
 };
 
+// The reader of onc_decode_heads: only the record's first P bytes exist (its
+// slot of the heads buffer). A read that ends past them — the parser has
+// already checked that it ends inside the record — yields zeros, touches no
+// memory and sets `past`, which stays set: the record is
+// ONC_EXTENT_HEAD_SHORT whatever the parse makes of the zeros (decode_kernel).
+struct RdHeads {
+    uintptr_t base;
+    uint32_t lim;
+    const uint32_t* col;
+    uint32_t P;              // record bytes that exist
+    mutable uint32_t past;   // a read ended past them
+
+    __device__ __forceinline__ uint32_t be32(uint32_t pos) const {
+        if (pos + 4u <= lim) return bswap(col[(pos >> 2) * kDecTile]);
+        if (pos + 4u <= P) return bswap(load4(base + pos));
+        past = 1u;
+        return 0u;
+    }
+
+    __device__ __forceinline__ void words16(uint32_t pos, uint32_t n, uint32_t out[ONC_MAX_GIDS]) const {
+        if (pos + 4u * n <= lim) {
+            const uint32_t* p = col + (pos >> 2) * kDecTile;
+#pragma unroll
+            for (uint32_t g = 0; g < ONC_MAX_GIDS; ++g) out[g] = g < n ? bswap(p[g * kDecTile]) : 0u;
+        } else if (pos + 4u * n <= P) {
+#pragma unroll
+            for (uint32_t g = 0; g < ONC_MAX_GIDS; ++g) out[g] = g < n ? bswap(load4(base + pos + 4u * g)) : 0u;
+        } else {
+            past = 1u;
+#pragma unroll
+            for (uint32_t g = 0; g < ONC_MAX_GIDS; ++g) out[g] = 0u;
+        }
+    }
+};
+
 #define ONC_RD(var)                                   \
     do {                                              \
         if (pos + 4u > end) return kShort;            \
@@ -829,9 +864,10 @@ __device__ __forceinline__ uint32_t stage_round2(uint32_t* s_win, int t, uintptr
 }
 
 template <int MODE, bool kExact = false, bool kNTOut = false, bool kFromLen = false, bool kBlkFused = false,
-          bool kRoot = false, bool kLine = false, bool kBound = false, bool kExtents = false>
+          bool kRoot = false, bool kLine = false, bool kBound = false, bool kExtents = false, bool kHeads = false>
 __global__ __launch_bounds__(kDecTile) void decode_kernel(DecArgs a) {
     static_assert(!kExtents || (kBound && !kFromLen && !kRoot), "extents: the bounded message decode only");
+    static_assert(!kHeads || (!kBound && !kFromLen && !kRoot && !kExtents), "heads: the message decode only");
     __shared__ uint32_t s_win[kWinWords * kDecTile];
     static_assert(kWinWords * kDecTile * 4 >= kDecTile * sizeof(onc_msg), "descriptor staging reuses the window");
     const int t = threadIdx.x;
@@ -888,6 +924,13 @@ __global__ __launch_bounds__(kDecTile) void decode_kernel(DecArgs a) {
             b = a.ext_start[i];
             L = a.ext_len[i];
         }
+    } else if constexpr (kHeads) {
+        // onc_decode_heads: the record's head is in its slot of the heads
+        // buffer (a.wire), its length is the caller's
+        if (valid) {
+            b = i * a.head_len;
+            L = a.rec_len[i];
+        }
     } else if (valid) {
         b = a.rec_off[i];
         L = a.rec_off[i + 1] - b;
@@ -914,12 +957,17 @@ __global__ __launch_bounds__(kDecTile) void decode_kernel(DecArgs a) {
     // Stage the window. Chunks past the record's last byte are not loaded;
     // empty records read nothing.
     constexpr bool kLineP = kLine && kPolicy;
+    // kHeads: both rounds are bounded by the bytes that exist, P = min(L,
+    // head_len), instead of the record's length (slots are 16-byte aligned:
+    // q0 == 0, and no chunk past P is loaded)
+    uint64_t Lw = L;
+    if constexpr (kHeads) Lw = min(L, uint64_t(a.head_len));
     uint32_t nch = 0, avail = 0, r44 = 0;
-    if (L != 0) nch = round1_chunks<kLineP, kPolicy>(win, q0, L, avail, r44);
+    if (L != 0) nch = round1_chunks<kLineP, kPolicy>(win, q0, Lw, avail, r44);
     u32x4 v1[kWin1L];
     load_round1<kLineP, ONC_DEC_COOP, kExtents && !ONC_EXT_FIRST_BASE>(s_win, t, win, nch, v1);
     uint32_t want = 0, last = 0;
-    if (L != 0) want = stage_round1<kLineP, kPolicy, kRoot>(s_win, t, base, q0, d0, L, needs2, v1, nch, avail, r44, last);
+    if (L != 0) want = stage_round1<kLineP, kPolicy, kRoot>(s_win, t, base, q0, d0, Lw, needs2, v1, nch, avail, r44, last);
     // round 2 (headers longer than round 1): cooperative under the standard
     // policy (the whole wave), else per lane
     constexpr bool kCoop2 = ONC_DEC_COOP2 && kPolicy && !kLineP;
@@ -958,6 +1006,30 @@ __global__ __launch_bounds__(kDecTile) void decode_kernel(DecArgs a) {
                 st = L > 0xFFFFFFFFull ? ONC_ERR_INVALID_LENGTH
                                        : parse_root<MODE>(R, uint32_t(L), b, i, a.root, a.param ? a.param[i] : 0u, m,
                                                           aux0, us, consumed);
+            }
+        } else if constexpr (kHeads) {
+            // the reader's window ends at P: the window's last chunk may
+            // reach past it into bytes that are not the record's
+            const uint32_t P = uint32_t(Lw);
+            const RdHeads RH{base, min(lim, P), &s_win[t], P, 0u};
+            st = parse_record<MODE>(RH, L, b, i, m, aux0, aux1, us);
+            // ONC_EXTENT_HEAD_SHORT: (a) a read ended past the head while
+            // ending inside the record; (b) the parse ended OK but the header
+            // — up to the payload's start, or the whole record when it has
+            // no payload — reaches past the head (a verifier body that is
+            // skipped, never read): every auth body and machine name of an OK
+            // record lies inside the heads buffer
+            bool head_short = RH.past != 0;
+            if (st == ONC_OK) {
+                const bool pay = m.msg_type == ONC_MSG_CALL ||
+                                 (m.reply_stat == ONC_REPLY_ACCEPTED && m.stat == ONC_ACCEPT_SUCCESS);
+                const uint64_t hdr_end = pay ? m.payload_off - b : L;
+                head_short = head_short || hdr_end > P;
+            }
+            if (head_short) {
+                st = ONC_DEC_BAD_EXTENT;
+                aux0 = kExtentHeadShort;
+                aux1 = 0;
             }
         } else {
             st = parse_record<MODE>(R, L, b, i, m, aux0, aux1, us);
@@ -1127,10 +1199,31 @@ hipError_t launch_extents_decode(const DecArgs& a, int mode, hipStream_t s) {
     return hipGetLastError();
 }
 
+// onc_decode_heads: the message decode with the heads prologue, loaders and
+// reader, per mode and first-round policy.
+template <bool kLine>
+hipError_t launch_heads_decode(const DecArgs& a, int mode, hipStream_t s) {
+    const dim3 g{uint32_t((a.n + kDecTile - 1) / kDecTile)}, b{uint32_t(kDecTile)};
+    if (mode == ONC_DECODE_BYTES)
+        ONC_LAUNCH((decode_kernel<ONC_DECODE_BYTES, true, true, false, false, false, kLine, false, false, true>), g, b, 0,
+                   s, a);
+    else
+        ONC_LAUNCH((decode_kernel<ONC_DECODE_SLICE, true, true, false, false, false, kLine, false, false, true>), g, b, 0,
+                   s, a);
+    return hipGetLastError();
+}
+
+// (The heads kernels are instantiated last, so they are laid out behind the
+// others in the code object and every older kernel keeps its place in it:
+// laid out in front of them they cost the configs[1] step, a decode whose
+// instructions are fetched anew after each encode, about 2 us.)
 hipError_t launch_decode(const DecArgs& a, int mode, hipStream_t s) {
-    if (a.extents) return a.line ? launch_extents_decode<true>(a, mode, s) : launch_extents_decode<false>(a, mode, s);
-    if (a.bounded) return launch_decode_any<true>(a, mode, s);
-    return launch_decode_any<false>(a, mode, s);
+    if (!a.head_len) {
+        if (a.extents) return a.line ? launch_extents_decode<true>(a, mode, s) : launch_extents_decode<false>(a, mode, s);
+        if (a.bounded) return launch_decode_any<true>(a, mode, s);
+        return launch_decode_any<false>(a, mode, s);
+    }
+    return a.line ? launch_heads_decode<true>(a, mode, s) : launch_heads_decode<false>(a, mode, s);
 }
 
 }  // namespace onc

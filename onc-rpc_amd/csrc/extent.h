@@ -21,6 +21,7 @@ constexpr uint32_t kExtentOk = 0;
 constexpr uint32_t kExtentStart = 1;     // the record starts past wire_len
 constexpr uint32_t kExtentEnd = 2;       // the record ends past wire_len
 constexpr uint32_t kExtentOrder = 3;     // rec_off[i + 1] < rec_off[i]
+constexpr uint32_t kExtentHeadShort = 4; // onc_decode_heads: the record's header does not fit its head
 
 // Record [b, b + L) against a wire of wire_len readable bytes. b == wire_len
 // with L == 0 is the legal empty slice &wire[len..len]. No sum is formed:

@@ -8,6 +8,7 @@
 
 #include "../../include/onc_rpc.h"
 #include "common.h"
+#include "defrag_heads_plan.h"
 #include "defrag_plan.h"
 #include "fragment_iov_plan.h"
 #include "fragment_plan.h"
@@ -154,6 +155,30 @@ struct DefragArgs {
     const uint32_t* frag_len;   // nfrag
 };
 
+// onc_defragment_heads (defrag_heads.hip). The plan kernels are
+// onc_defragment_extents' (a DefragArgs whose E is the caller's frag_pre);
+// scratch per fragment in onc_defragment's buffer: S (8 bytes), M and the
+// codec's record lengths (4 each).
+struct HeadsArgs {
+    const uint8_t* wire;
+    const uint64_t* frag_start; // nfrag
+    const uint32_t* frag_len;   // nfrag
+    uint64_t nfrag;
+    uint32_t head_len;          // a multiple of 16 in [64, 4096]
+    uint8_t* heads;             // 16-byte aligned: slot r at r * head_len
+    uint64_t max_records;       // slots
+    uint32_t* rec_len;          // nfrag
+    uint64_t* rec_frag;         // nfrag + 1
+    uint64_t* frag_pre;         // nfrag (the plan's E)
+    int32_t* status;            // nfrag
+    uint64_t* result;           // [6]
+    const uint64_t* S;          // nfrag: the fragment's record index
+    const uint32_t* M;          // nfrag: 1 for the first fragment of a record
+    const uint32_t* lens;       // nfrag: record lengths (0: ONC_ENC_TOO_LONG)
+    const DefragAgg* blk;       // per 256 fragments (+ 1: the whole batch)
+    const uint64_t* info;       // [0] n_multi
+};
+
 // onc_fragment (fragment.hip). Scratch per record: E (8 bytes) and the block
 // sums (24 per 256 records), in onc_defragment's buffer; the copy takes a
 // record's source and body length from the caller's rec_off.
@@ -223,6 +248,10 @@ struct DecArgs {
     const uint64_t* ext_start;  // per record: its first byte's wire offset
     const uint32_t* ext_len;    // per record: its length
     uint32_t extents;           // 1: the extents kernels (decode_kernel<..., kExtents>; always bounded)
+    // onc_decode_heads (appended: the fields above keep their kernarg offsets):
+    // `wire` is the heads buffer, record i's first min(rec_len[i], head_len)
+    // bytes at i * head_len
+    uint32_t head_len;          // != 0: the heads kernels (decode_kernel<..., kHeads>)
 };
 
 // onc_frame_streams (streams.hip). Scratch per segment: base and x (8 bytes
@@ -328,6 +357,10 @@ hipError_t launch_defrag_blkscan(const DefragArgs& a, hipStream_t s);
 hipError_t launch_defrag_frag(const DefragArgs& a, hipStream_t s);
 hipError_t launch_defrag_place(const DefragArgs& a, hipStream_t s);
 hipError_t launch_defrag_copy(const DefragArgs& a, hipStream_t s);
+// defrag_heads.hip
+hipError_t launch_heads_empty(const HeadsArgs& a, hipStream_t s);
+hipError_t launch_heads_place(const HeadsArgs& a, hipStream_t s);
+hipError_t launch_heads_gather(const HeadsArgs& a, hipStream_t s);
 // fragment.hip
 hipError_t launch_fragp_blk(const FragmentArgs& a, hipStream_t s);
 hipError_t launch_fragp_blkscan(const FragmentArgs& a, hipStream_t s);

@@ -59,6 +59,8 @@ STATUS = {
 # aux0 = the reason, in the order the checks are made
 DEC_BAD_EXTENT = 106
 EXTENT_START_PAST_WIRE, EXTENT_END_PAST_WIRE, EXTENT_NOT_MONOTONIC = 1, 2, 3
+EXTENT_HEAD_SHORT = 4        # onc_decode_heads: the record's header does not fit its head
+HEAD_SPAN_MAX = 724          # the furthest the message parse reaches into a record (ONC_HEAD_SPAN_MAX)
 
 # --- dtypes ------------------------------------------------------------------
 MSG_DTYPE = np.dtype({

@@ -44,6 +44,7 @@ EXPORTED = [
     "onc_frame_streams", "onc_decode_extents",
     "onc_fragment", "onc_fragment_iov",
     "onc_frame_fragment_streams", "onc_defragment_extents",
+    "onc_defragment_heads", "onc_decode_heads",
 ]
 
 # onc_codec_options (include/onc_rpc.h)
@@ -131,6 +132,8 @@ def load_library(path=LIB_PATH):
     lib.onc_decode_extents.argtypes = [vp, vp, u64, vp, vp, u64, i32, C.POINTER(OncDecoded)]
     lib.onc_frame_fragment_streams.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp]
     lib.onc_defragment_extents.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, vp, vp]
+    lib.onc_defragment_heads.argtypes = [vp, vp, vp, vp, u64, C.c_uint32, vp, u64, vp, vp, vp, vp, vp]
+    lib.onc_decode_heads.argtypes = [vp, vp, C.c_uint32, vp, u64, i32, C.POINTER(OncDecoded)]
     for name in EXPORTED:
         getattr(lib, name).restype = getattr(lib, name).restype or i32
     # a stale library would read a differently laid out onc_batch and label
@@ -380,7 +383,29 @@ class Codec:
                                                     cap, _ptr(rec_off), _ptr(status), _ptr(result)),
                     "onc_defragment_extents")
 
+    def defragment_heads(self, wire, frag_start, frag_len, nfrag, head_len, heads, max_records, rec_len, rec_frag,
+                         frag_pre, status, result):
+        """onc_defragment_heads: the first head_len bytes of every record of
+        the fragments wire[frag_start[j], +frag_len[j]) into fixed-stride
+        slots (`heads`: a tensor or an int device pointer); rec_frag /
+        frag_pre locate the rest; result = 6 words, result[2] the heads bytes
+        the batch needs."""
+        hptr = C.c_void_p(heads) if isinstance(heads, int) else _ptr(heads)
+        self._check(self.lib.onc_defragment_heads(self.h, _ptr(wire), _ptr(frag_start), _ptr(frag_len), nfrag, head_len,
+                                                  hptr, max_records, _ptr(rec_len), _ptr(rec_frag), _ptr(frag_pre),
+                                                  _ptr(status), _ptr(result)), "onc_defragment_heads")
+
     # -- decode -----------------------------------------------------------
+    def decode_heads(self, heads, head_len, rec_len, n, mode, msgs, unix, status, aux0, aux1):
+        """onc_decode_heads: record i has rec_len[i] bytes, of which the first
+        min(rec_len[i], head_len) are at heads + i * head_len; offsets in the
+        outputs are relative to `heads` (a tensor or an int device pointer)."""
+        d = OncDecoded(msgs.data_ptr(), unix.data_ptr(), status.data_ptr(), aux0.data_ptr(),
+                       aux1.data_ptr())
+        hptr = C.c_void_p(heads) if isinstance(heads, int) else _ptr(heads)
+        self._check(self.lib.onc_decode_heads(self.h, hptr, head_len, _ptr(rec_len), n, mode, C.byref(d)),
+                    "onc_decode_heads")
+
     def decode_extents(self, wire, wire_len, rec_start, rec_len, n, mode, msgs, unix, status, aux0, aux1):
         """onc_decode_extents: record i = wire[rec_start[i], +rec_len[i]), in
         any order, bounded by wire_len (2**64 - 1: the extents are trusted)."""
@@ -735,6 +760,68 @@ def decode_host_extents(codec: Codec, wire: np.ndarray, rec_start, rec_len, mode
     bufs = DecodeBuffers(n, device)
     codec.decode_extents(w, len(wire) if wire_len is None else wire_len, st, ln, n, mode, bufs.msgs, bufs.unix,
                          bufs.status, bufs.aux0, bufs.aux1)
+    codec.sync()
+    return bufs.to_host()
+
+
+def aligned_bytes(nbytes, fill=0, device="cuda"):
+    """(tensor, lo): a uint8 device tensor whose element lo is 16-byte aligned
+    with nbytes usable bytes from there and 16 bytes behind them, every byte
+    `fill`."""
+    torch = _torch()
+    base = torch.full((16 + nbytes + 16,), fill, dtype=torch.uint8, device=device)
+    return base, (-base.data_ptr()) % 16
+
+
+def defragment_host_heads(codec: Codec, wire, frag_start, frag_len, head_len, max_records=None, fill=0, device="cuda"):
+    """Convenience: host wire bytes and fragment extents ->
+    onc_defragment_heads -> a dict of host arrays: heads (max_records *
+    head_len bytes, `fill` where nothing was written; max_records None: one
+    slot per fragment), rec_len[n], rec_frag[n+1], frag_pre[nfrag], status[n],
+    result[6], and `raw`: the whole output arrays, pre-filled with sentinels
+    (-1; heads `fill`), so that a caller can see what was left alone."""
+    torch = _torch()
+    fs = np.ascontiguousarray(frag_start, np.uint64)
+    fl = np.ascontiguousarray(frag_len, np.uint32)
+    nfrag = len(fs)
+    w = to_device(np.frombuffer(bytes(wire) + b"\0" * 16, np.uint8), device)
+    d_fs = torch.from_numpy(np.append(fs, np.uint64(0)).view(np.int64).copy()).to(device)
+    d_fl = torch.from_numpy(np.append(fl, np.uint32(0)).view(np.int32).copy()).to(device)
+    slots = nfrag if max_records is None else max_records
+    base, lo = aligned_bytes(slots * head_len + head_len, fill, device)     # one slot more: a stray write shows
+    rec_len = torch.full((nfrag + 1,), -1, dtype=torch.int32, device=device)
+    rec_frag = torch.full((nfrag + 2,), -1, dtype=torch.int64, device=device)
+    frag_pre = torch.full((nfrag + 1,), -1, dtype=torch.int64, device=device)
+    status = torch.full((nfrag + 1,), -1, dtype=torch.int32, device=device)
+    res = torch.full((6,), -1, dtype=torch.int64, device=device)
+    codec.defragment_heads(w, d_fs, d_fl, nfrag, head_len, base.data_ptr() + lo, slots, rec_len, rec_frag, frag_pre,
+                           status, res)
+    codec.sync()
+    r = res.cpu().numpy().view(np.uint64).copy()
+    n = int(r[0])
+    raw = {"heads": base.cpu().numpy()[lo:lo + slots * head_len + head_len].copy(),
+           "rec_len": rec_len.cpu().numpy().view(np.uint32).copy(),
+           "rec_frag": rec_frag.cpu().numpy().view(np.uint64).copy(),
+           "frag_pre": frag_pre.cpu().numpy().view(np.uint64).copy(), "status": status.cpu().numpy().copy()}
+    return {"heads": raw["heads"][:slots * head_len], "rec_len": raw["rec_len"][:n], "rec_frag": raw["rec_frag"][:n + 1],
+            "frag_pre": raw["frag_pre"][:nfrag], "status": raw["status"][:n], "result": r, "raw": raw}
+
+
+def decode_host_heads(codec: Codec, heads, head_len, rec_len, mode, device="cuda"):
+    """Convenience: host heads (n * head_len bytes) and record lengths ->
+    onc_decode_heads -> host arrays, as decode_host_wire."""
+    torch = _torch()
+    ln = np.ascontiguousarray(rec_len, np.uint32)
+    n = len(ln)
+    raw = np.frombuffer(bytes(heads), np.uint8)
+    assert len(raw) >= n * head_len
+    base, lo = aligned_bytes(max(len(raw), 16), 0, device)
+    if len(raw):
+        base[lo:lo + len(raw)] = torch.from_numpy(raw.copy()).to(device)
+    d_ln = torch.from_numpy(np.append(ln, np.uint32(0)).view(np.int32).copy()).to(device)
+    bufs = DecodeBuffers(n, device)
+    codec.decode_heads(base.data_ptr() + lo, head_len, d_ln, n, mode, bufs.msgs, bufs.unix, bufs.status, bufs.aux0,
+                       bufs.aux1)
     codec.sync()
     return bufs.to_host()
 
