@@ -4,7 +4,8 @@
 // bytes that exist, the result words, and which fragment of a record holds a
 // body byte. The record arithmetic itself (B_r, the mark, the scan state) is
 // defrag_plan.h's. Plain C++ without HIP headers, as defrag_plan.h: a host
-// program drives it at sizes no GPU test can be given.
+// program drives it up to sizes no buffer has; on the device
+// tests/test_gpu_beyond_4gib.py runs it over 4.4 GB of fragments.
 #pragma once
 
 #include <stdint.h>

@@ -5,7 +5,9 @@
 // record is what RpcMessage::serialise_into writes (rpc_message.rs:146-156:
 // one mark with the last-fragment bit and the body length, a body of 2^31
 // bytes or more refused). Plain C++ without HIP headers, as extent.h: a host
-// program drives it at sizes no GPU test can be given.
+// program drives it up to sizes no buffer has; on the device
+// tests/test_gpu_beyond_4gib.py runs it over 4.4 GB of fragments and on one
+// record of more than 2^32 bytes.
 #pragma once
 
 #include <stdint.h>

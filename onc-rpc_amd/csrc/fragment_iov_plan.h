@@ -10,7 +10,8 @@
 // inside. The closed-form map from a piece's index inside the record back to
 // (fragment, part) needs no table and no search. Plain C++ without HIP
 // headers, as fragment_plan.h: tests/cpp_fragment_iov/plan_probe.cpp drives it
-// at lengths no GPU test can be given. hdr_len and payload_len are 32 bits, so
+// at every length; on the device tests/test_gpu_far_offsets.py runs it on
+// entries that name 4 GiB payloads (nothing is read behind an entry). hdr_len and payload_len are 32 bits, so
 // B < 2^33, k <= 2^33 and a record has at most 2^34 + 1 pieces.
 #pragma once
 

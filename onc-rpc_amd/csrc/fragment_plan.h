@@ -8,8 +8,9 @@
 // "last". The input record is one fragment as RpcMessage::serialise_into
 // writes it (rpc_message.rs:146-156); its own mark is never read: B = L - 4.
 // Plain C++ without HIP headers, as defrag_plan.h: a host program
-// (tests/cpp_fragment/plan_probe.cpp) drives it at sizes no GPU test can be
-// given. Exact for L < 2^61 (the output length, at most 5 B, fits 64 bits).
+// (tests/cpp_fragment/plan_probe.cpp) drives it up to sizes no buffer has; on
+// the device tests/test_gpu_beyond_4gib.py runs it over a 4.4 GB stream and
+// over one extent of that length (frag_at's 64-bit branch). Exact for L < 2^61 (the output length, at most 5 B, fits 64 bits).
 #pragma once
 
 #include <stdint.h>

@@ -1,6 +1,6 @@
 // plan_probe.cpp — the record arithmetic of onc_fragment
-// (onc-rpc_amd/csrc/fragment_plan.h) at sizes no GPU test can be given, on the
-// CPU: compiled with the host compiler (and -fsanitize=undefined where the
+// (onc-rpc_amd/csrc/fragment_plan.h) up to sizes no buffer has (the GPU tests
+// stop at a 4.4 GB stream, tests/test_gpu_beyond_4gib.py), on the CPU: compiled with the host compiler (and -fsanitize=undefined where the
 // toolchain has it) and run by tests/test_fragment_host.py. The kernels call
 // the same functions.
 #include <cstdint>

@@ -3,8 +3,8 @@
 // compiler (and -fsanitize=undefined where the toolchain has it) and run by
 // tests/test_fragment_iov_host.py. The kernels call the same functions. The
 // piece map is checked against a walk over the fragments as the loop in
-// include/onc_rpc.h writes them, the 64-bit counts at lengths no GPU test can
-// be given, both capacity tests near 2^64, and the plan's scan at every
+// include/onc_rpc.h writes them, the 64-bit counts at every length (on the GPU:
+// tests/test_gpu_far_offsets.py, entries of 4 GiB), both capacity tests near 2^64, and the plan's scan at every
 // blocking of a record list.
 #include <cstdint>
 #include <cstdio>

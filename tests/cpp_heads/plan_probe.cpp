@@ -1,6 +1,6 @@
 // plan_probe.cpp — the host arithmetic of onc_defragment_heads
-// (onc-rpc_amd/csrc/defrag_heads_plan.h) driven by a host program at sizes no
-// GPU test can be given: the serial loop of include/onc_rpc.h run with that
+// (onc-rpc_amd/csrc/defrag_heads_plan.h) driven by a host program up to sizes
+// no buffer has (the GPU tests stop at 4.4 GB): the serial loop of include/onc_rpc.h run with that
 // arithmetic over fragment lists built here — ONC_ENC_TOO_LONG at B = 2^31 - 1
 // / 2^31, the capacity cut, the result words, the head_len rule — and the
 // fragment search against a brute-force walk, with runs of empty fragments.

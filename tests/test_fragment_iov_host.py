@@ -2,8 +2,9 @@
 fragments without a copy): the symbol and its argument checks, and the record
 arithmetic the kernels call (onc-rpc_amd/csrc/fragment_iov_plan.h) in a
 stand-alone host program — the piece map against a brute-force walk, entries
-of 2^32 - 1 header and payload bytes, both capacities near 2^64 — none of
-which a GPU test can be given."""
+of 2^32 - 1 header and payload bytes, both capacities near 2^64. (On the GPU
+tests/test_gpu_far_offsets.py gives the kernels entries of 4 GiB payloads;
+the capacities near 2^64 stay here.)"""
 import ctypes as C
 import os
 import subprocess
