@@ -87,7 +87,9 @@ extern "C" {
  *    onc_defragment_heads and onc_decode_heads (fragmented records decoded
  *    without copying their payloads), which add no status code and no timing
  *    id: the one new outcome is a reason of ONC_DEC_BAD_EXTENT,
- *    ONC_EXTENT_HEAD_SHORT. */
+ *    ONC_EXTENT_HEAD_SHORT; onc_piece_offsets and onc_gather_pieces with
+ *    onc_gather_src (a piece list written as one stream on the device), which
+ *    add no status code and reuse onc_defragment's timing ids. */
 #define ONC_RPC_ABI_VERSION 8
 
 /* ------------------------------------------------------------------------ */
@@ -1172,6 +1174,92 @@ int onc_fragment_iov(onc_codec* codec, const onc_iov_rec* iov, uint64_t n,
                      onc_frag_piece* pieces, uint64_t max_pieces,
                      uint64_t* out_off /*[dev, n + 1]*/, uint64_t* piece_off /*[dev, n + 1]*/,
                      int32_t* status /*[dev, n]*/, uint64_t* result /*[dev, 4]*/);
+
+/* A piece list written as one stream on the device: what a writev() of the
+ * pieces sends, gathered straight from the three sources into one contiguous
+ * buffer, a window of the stream at a time — each payload byte moves once,
+ * where onc_encode + onc_fragment move it twice. The stream is the pieces back
+ * to back; piece i is pieces[i].len bytes at byte pieces[i].off of source
+ * pieces[i].src (ONC_PIECE_MARK / _HDR / _PAYLOAD index base[] and len[]). Any
+ * list is accepted, not only onc_fragment_iov's: pieces of no bytes anywhere
+ * (long runs of them too), pieces that repeat, overlap and stand in any source
+ * order. A piece is OK when it lies inside its source,
+ *
+ *   ok(p) = p.len == 0 or (p.src <= 2 and p.off <= len[p.src] and p.len <= len[p.src] - p.off)
+ *
+ * (no sum is formed: off + len may wrap near 2^64), and bad otherwise. A bad
+ * piece keeps its place in the stream but is never read: its bytes of `out`
+ * are left as they were and its neighbours are unaffected.
+ *
+ * onc_piece_offsets: where every piece starts in the stream, and the bad ones
+ * counted. The result is exactly that of
+ *
+ *   pos = bad = 0; first_bad = npieces
+ *   for i in 0 .. npieces-1:
+ *       piece_pos[i] = pos
+ *       if !ok(pieces[i]): bad += 1; first_bad = min(first_bad, i)
+ *       pos += pieces[i].len
+ *   piece_pos[npieces] = pos; result = {pos, bad, first_bad}
+ *
+ * onc_gather_pieces: stream bytes [from, from + count) into out[0, count), as
+ * far as the stream goes. The result is exactly that of
+ *
+ *   end = from + count                                   # 64-bit, saturating
+ *   for i in 0 .. npieces-1:
+ *       a = max(piece_pos[i], from); b = min(piece_pos[i] + pieces[i].len, end)
+ *       if a < b and ok(pieces[i]):
+ *           out[a - from, b - from) = base[src_i][off_i + (a - piece_pos[i]), off_i + (b - piece_pos[i]))
+ *
+ *   src[host]       : the three sources' device addresses and lengths, read
+ *                     by the call itself (not by the kernels). base[k] may be
+ *                     NULL when len[k] is 0.
+ *   piece_pos[dev, npieces + 1]: onc_piece_offsets writes it, onc_gather_pieces
+ *                     reads it (as written for the same pieces and sources; it
+ *                     is trusted). 8-byte aligned; pieces 16-byte aligned.
+ *   result[dev, 3]  : {stream bytes (= piece_pos[npieces]), bad pieces, index
+ *                     of the first bad piece (npieces: none)}.
+ *   out[dev]        : any byte address (as onc_encode), device memory or
+ *                     mapped host memory (a send buffer); must not overlap the
+ *                     sources, pieces or piece_pos. No byte before out, at or
+ *                     after out + count, or at or past stream position
+ *                     piece_pos[npieces] is written. Whole aligned 16-byte
+ *                     chunks of out that lie inside one OK piece go with one
+ *                     load and one store; the ends of the window and chunks
+ *                     that span pieces are resolved byte by byte (such a
+ *                     chunk is still stored at once when all 16 of its bytes
+ *                     are written).
+ * Source reads follow onc_decode's rule: only whole aligned 16-byte granules
+ * that hold bytes of an OK piece inside the window, so a mapped host source
+ * stays cheap. The stream must be shorter than 2^64 bytes.
+ *  - ONC_RC_EINVAL: a NULL codec, src or piece_pos; a NULL result
+ *    (onc_piece_offsets); NULL pieces with npieces > 0; NULL out with
+ *    count > 0 (onc_gather_pieces); a source with len > 0 and a NULL base.
+ *    ONC_RC_EALIGN: pieces not 16-byte aligned or piece_pos not 8-byte aligned.
+ *  - npieces == 0 gives piece_pos[0] = 0 and the result {0, 0, 0}, and a gather
+ *    that writes nothing; count == 0 writes nothing.
+ * Both calls are asynchronous on the codec's stream and every step is a kernel
+ * launch (no memset or memcpy node in a captured call). Scratch:
+ * onc_piece_offsets keeps its block sums (24 bytes per 256 pieces: under 1
+ * byte per piece) in onc_defragment's buffer: onc_codec_reserve(max_records
+ * >= npieces) covers it; growing it inside a capture is ONC_RC_ECAPTURE.
+ * onc_gather_pieces uses none. The offsets' launches report under
+ * ONC_K_DEFRAG_PLAN and the gather under ONC_K_DEFRAG_COPY.
+ * Kernels (gather.hip): onc_fragment's plan shape (block sums, one-workgroup
+ * scan, apply) over {bytes, bad, first bad}, and onc_defragment's copy with
+ * three source bases and no mark: partitioned by output bytes (a wave per
+ * 8 KiB tile of the window), the pieces reaching into a tile staged in LDS. */
+typedef struct onc_gather_src {          /* indexed by ONC_PIECE_MARK / _HDR / _PAYLOAD */
+    const uint8_t* base[3];              /* [dev]; may be NULL when len is 0 */
+    uint64_t       len[3];               /* bytes in each source */
+} onc_gather_src;
+
+int onc_piece_offsets(onc_codec* codec, const onc_frag_piece* pieces, uint64_t npieces,
+                      const onc_gather_src* src /*host*/,
+                      uint64_t* piece_pos /*[dev, npieces + 1]*/, uint64_t* result /*[dev, 3]*/);
+
+int onc_gather_pieces(onc_codec* codec, const onc_frag_piece* pieces, const uint64_t* piece_pos,
+                      uint64_t npieces, const onc_gather_src* src /*host*/,
+                      uint64_t from, uint64_t count, uint8_t* out);
 
 /* Exclusive scan of record lengths into offsets:
  * rec_off[0] = base, rec_off[i+1] = rec_off[i] + rec_len[i]  ([dev]). */

@@ -30,7 +30,9 @@
 //                   one onc_encode_body call (one pass, no length pass);
 //                   serialise_vectored is its zero-copy form: headers only,
 //                   the records fragmented as a writev() list of pieces
-//                   (onc_encode_iov + onc_fragment_iov).
+//                   (onc_encode_iov + onc_fragment_iov), and
+//                   serialise_fragmented that list gathered into bytes by
+//                   the device (onc_piece_offsets + onc_gather_pieces).
 //   BatchDecoder  — the caller's try_from loop over many records, one
 //                   onc_decode_lengths_bounded call (a record length that
 //                   runs past the wire is Error(ONC_DEC_BAD_EXTENT), unread).
@@ -627,6 +629,31 @@ struct VectoredStream {
         }
         return out;
     }
+    // Stream bytes [from, from + count), as far as the stream goes: what
+    // onc_gather_pieces writes for that window (from + count saturates).
+    std::vector<uint8_t> gather_window(uint64_t from, uint64_t count, const uint8_t* payload_arena) const {
+        std::vector<uint8_t> out;
+        const uint64_t end = count > ~uint64_t(0) - from ? ~uint64_t(0) : from + count;
+        uint64_t pos = 0;
+        for (size_t i = 0; i < pieces.size(); ++i) {
+            const auto p = piece_ptr(i, payload_arena);
+            const uint64_t a = std::max(pos, from), b = std::min(pos + p.second, end);
+            if (a < b) out.insert(out.end(), p.first + (a - pos), p.first + (b - pos));
+            pos += p.second;
+        }
+        return out;
+    }
+};
+
+// What BatchEncoder::serialise_fragmented returns: the fragmented stream as
+// bytes. Message m's fragments are bytes[out_off[m], out_off[m + 1]); a
+// message that fails (status[m] != ONC_OK) has none.
+struct FragmentedStream {
+    std::vector<uint8_t> bytes;
+    std::vector<uint64_t> out_off;         // n + 1
+    std::vector<int32_t> status;           // per message: ONC_OK or ONC_ENC_*
+    size_t n_frags = 0;                    // fragments
+    size_t n_multi = 0;                    // messages cut into more than one fragment
 };
 
 // ----------------------------------------------------------------------------
@@ -673,6 +700,18 @@ public:
     // of pieces (onc_fragment_iov) — nothing is copied. Throws CodecError for
     // a body-level batch or a max_frag outside 1 .. 0x7FFFFFFF.
     VectoredStream serialise_vectored(Codec& codec, uint32_t max_frag = 0x7FFFFFFFu);
+    // serialise_vectored's stream as bytes, written once by the device:
+    // onc_encode_iov -> onc_fragment_iov -> onc_piece_offsets ->
+    // onc_gather_pieces, straight from the marks, the headers and the payload
+    // arena into the codec's mapped staging (no packed intermediate, as
+    // serialise_into + fragment_stream make). rec_limits, if given, holds a
+    // fragment limit per message (size() values; max_frag is then ignored but
+    // must still be valid): a message whose own limit is outside
+    // 1 .. 0x7FFFFFFF gets ONC_ENC_BAD_DESCRIPTOR and contributes nothing.
+    // Throws CodecError for a body-level batch, a max_frag outside
+    // 1 .. 0x7FFFFFFF or a rec_limits of another size.
+    FragmentedStream serialise_fragmented(Codec& codec, uint32_t max_frag = 0x7FFFFFFFu,
+                                          const std::vector<uint32_t>* rec_limits = nullptr);
     // The payload bytes ONC_PIECE_PAYLOAD pieces point into: valid until the
     // next push() or clear().
     const std::vector<uint8_t>& payload_arena() const { return payload_; }
@@ -1205,6 +1244,103 @@ inline VectoredStream BatchEncoder::serialise_vectored(Codec& codec, uint32_t ma
     r.n_frags = nf;
     r.n_multi = size_t(d[2]);
     r.bytes = d[1];
+    return r;
+}
+
+// serialise_vectored's steps with the stream gathered on the device: after the
+// plan the stage grows by the marks, the pieces, their positions and the
+// stream itself (it keeps the batch, the headers and the entries; every
+// pointer is re-derived from its offset), and the sources of the gather are the
+// stage's own regions.
+inline FragmentedStream BatchEncoder::serialise_fragmented(Codec& codec, uint32_t max_frag,
+                                                           const std::vector<uint32_t>* rec_limits) {
+    using detail::need;
+    if (root() != ONC_ROOT_RPC_MESSAGE) throw CodecError("serialise_fragmented: a body-level batch has no record marks");
+    if (max_frag < 1 || max_frag > 0x7FFFFFFFu) throw CodecError("serialise_fragmented: max_frag outside 1 .. 0x7FFFFFFF");
+    const size_t n = msgs_.size();
+    if (rec_limits && rec_limits->size() != n) throw CodecError("serialise_fragmented: one limit per message");
+    FragmentedStream r;
+    r.out_off.assign(n + 1, 0);
+    r.status.assign(n, ONC_OK);
+    if (!n) return r;
+    const size_t hcap = 1024 * n;
+    detail::Carve c{codec.stage(staged_bytes() + need<uint8_t>(hcap) + need<onc_iov_rec>(n) + 2 * need<int32_t>(n) +
+                                need<uint32_t>(n) + 2 * need<uint64_t>(n + 1) + need<uint64_t>(4) + need<uint64_t>(3))};
+    const onc_batch b = stage_batch(c);
+    const size_t pay_at = size_t(b.payload_arena - c.s.dev);
+    const size_t hdr_at = c.off;
+    const auto hdr = c.take<uint8_t>(hcap);
+    const size_t iov_at = c.off;
+    c.take<onc_iov_rec>(n);
+    const auto st = c.take<int32_t>(n);
+    const size_t fst_at = c.off;
+    c.take<int32_t>(n);
+    const size_t lim_at = c.off;
+    const auto lim = c.take<uint32_t>(n);
+    const size_t off_at = c.off;
+    c.take<uint64_t>(n + 1);
+    const size_t poff_at = c.off;
+    c.take<uint64_t>(n + 1);
+    const size_t res_at = c.off;
+    const auto res = c.take<uint64_t>(4);
+    const size_t gres_at = c.off;
+    c.take<uint64_t>(3);
+    if (rec_limits) std::memcpy(lim.host, rec_limits->data(), n * 4);
+    auto iov = [&] { return reinterpret_cast<onc_iov_rec*>(c.s.dev + iov_at); };
+    codec.check(onc_encode_iov(codec.get(), &b, hdr.dev, hcap, iov(), st.dev, res.dev), "onc_encode_iov");
+    codec.sync();
+    std::memcpy(r.status.data(), st.host, n * 4);
+    const uint64_t hdr_len = res.host[0];
+    // a failing message writes nothing: placeholder entries emptied (ABI 8)
+    for (size_t i = 0; i < n; ++i) {
+        if (r.status[i] != ONC_OK) {
+            codec.check(onc_compact_iov(codec.get(), iov(), st.dev, n, nullptr), "onc_compact_iov");
+            break;
+        }
+    }
+    auto fragment = [&](uint8_t* marks, uint64_t marks_cap, onc_frag_piece* pieces, uint64_t max_pieces) {
+        uint8_t* d = c.s.dev;
+        codec.check(onc_fragment_iov(codec.get(), iov(), n, max_frag,
+                                     rec_limits ? reinterpret_cast<const uint32_t*>(d + lim_at) : nullptr, marks, marks_cap,
+                                     pieces, max_pieces, reinterpret_cast<uint64_t*>(d + off_at),
+                                     reinterpret_cast<uint64_t*>(d + poff_at), reinterpret_cast<int32_t*>(d + fst_at),
+                                     reinterpret_cast<uint64_t*>(d + res_at)),
+                    "onc_fragment_iov");
+    };
+    fragment(nullptr, 0, nullptr, 0);
+    codec.sync();
+    uint64_t d[4];
+    std::memcpy(d, c.s.host + res_at, sizeof(d));
+    const size_t nf = size_t(d[0]), np = size_t(d[3]), total = size_t(d[1]);
+    const size_t kept = c.off;
+    c.s = codec.stage(kept + need<uint8_t>(4 * nf) + need<onc_frag_piece>(np) + need<uint64_t>(np + 1) + need<uint8_t>(total),
+                      kept);
+    const auto marks = c.take<uint8_t>(4 * nf);
+    const auto pieces = c.take<onc_frag_piece>(np);
+    const auto pos = c.take<uint64_t>(np + 1);
+    const auto out = c.take<uint8_t>(total);
+    fragment(marks.dev, 4 * nf, pieces.dev, np);
+    onc_gather_src src{};
+    src.base[ONC_PIECE_MARK] = marks.dev;
+    src.len[ONC_PIECE_MARK] = 4 * nf;
+    src.base[ONC_PIECE_HDR] = c.s.dev + hdr_at;
+    src.len[ONC_PIECE_HDR] = hdr_len;
+    src.base[ONC_PIECE_PAYLOAD] = c.s.dev + pay_at;
+    src.len[ONC_PIECE_PAYLOAD] = payload_.size();
+    uint64_t* gres = reinterpret_cast<uint64_t*>(c.s.dev + gres_at);
+    codec.check(onc_piece_offsets(codec.get(), pieces.dev, np, &src, pos.dev, gres), "onc_piece_offsets");
+    codec.check(onc_gather_pieces(codec.get(), pieces.dev, pos.dev, np, &src, 0, total, out.dev), "onc_gather_pieces");
+    codec.sync();
+    uint64_t g[3];
+    std::memcpy(g, c.s.host + gres_at, sizeof(g));
+    if (g[0] != total || g[1] != 0) throw CodecError("serialise_fragmented: the piece list does not match its sources");
+    const int32_t* fs = reinterpret_cast<const int32_t*>(c.s.host + fst_at);
+    for (size_t i = 0; i < n; ++i)
+        if (r.status[i] == ONC_OK) r.status[i] = fs[i];      // ONC_ENC_BAD_DESCRIPTOR: its own limit is no fragment size
+    r.bytes.assign(out.host, out.host + total);
+    std::memcpy(r.out_off.data(), c.s.host + off_at, (n + 1) * 8);
+    r.n_frags = nf;
+    r.n_multi = size_t(d[2]);
     return r;
 }
 

@@ -1585,6 +1585,65 @@ int onc_fragment_iov(onc_codec* c, const onc_iov_rec* iov, uint64_t n, uint32_t 
     return run(c, ONC_K_DEFRAG_COPY, "fragiov_fill", [&] { return onc::launch_fragiov_fill(a, c->stream); });
 }
 
+// The checks onc_piece_offsets and onc_gather_pieces share, and the sources.
+static int gather_args(const onc_codec* c, const onc_frag_piece* pieces, const uint64_t* piece_pos, uint64_t npieces,
+                       const onc_gather_src* src, onc::GatherArgs& a) {
+    if (!c || !src || !piece_pos || (npieces && !pieces)) return ONC_RC_EINVAL;
+    for (int k = 0; k < 3; ++k)
+        if (src->len[k] && !src->base[k]) return ONC_RC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(pieces) & 15) || (reinterpret_cast<uintptr_t>(piece_pos) & 7)) return ONC_RC_EALIGN;
+    a.pieces = pieces;
+    a.npieces = npieces;
+    a.base0 = src->base[0];
+    a.base1 = src->base[1];
+    a.base2 = src->base[2];
+    a.len0 = src->len[0];
+    a.len1 = src->len[1];
+    a.len2 = src->len[2];
+    a.piece_pos = const_cast<uint64_t*>(piece_pos);
+    return ONC_RC_OK;
+}
+
+int onc_piece_offsets(onc_codec* c, const onc_frag_piece* pieces, uint64_t npieces, const onc_gather_src* src,
+                      uint64_t* piece_pos, uint64_t* result) {
+    if (!result) return ONC_RC_EINVAL;
+    onc::GatherArgs a{};
+    int rc = gather_args(c, pieces, piece_pos, npieces, src, a);
+    if (rc != ONC_RC_OK) return rc;
+    a.result = result;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    if (npieces == 0)
+        return run(c, ONC_K_DEFRAG_PLAN, "gath_empty", [&] { return onc::launch_gath_empty(a, c->stream); });
+    // onc_defragment's buffer, a piece where it keeps a fragment: the block
+    // sums alone (24 (npieces / 256 + 2) bytes of its 28 per fragment)
+    rc = ensure_defrag(c, npieces);
+    if (rc != ONC_RC_OK) return rc;
+    a.blk = reinterpret_cast<onc::GatherAgg*>(c->dfr);
+    static_assert(sizeof(onc::GatherAgg) == 24, "the block sums fit the first array: 24 (F / 256 + 2) <= 8 (F + 2)");
+    rc = run(c, ONC_K_DEFRAG_PLAN, "gath_blk", [&] { return onc::launch_gath_blk(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "gath_blkscan", [&] { return onc::launch_gath_blkscan(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "gath_apply", [&] { return onc::launch_gath_apply(a, c->stream); });
+    return rc;
+}
+
+int onc_gather_pieces(onc_codec* c, const onc_frag_piece* pieces, const uint64_t* piece_pos, uint64_t npieces,
+                      const onc_gather_src* src, uint64_t from, uint64_t count, uint8_t* out) {
+    if (!out && count) return ONC_RC_EINVAL;
+    onc::GatherArgs a{};
+    const int rc = gather_args(c, pieces, piece_pos, npieces, src, a);
+    if (rc != ONC_RC_OK) return rc;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    if (npieces == 0 || count == 0) return ONC_RC_OK;     // nothing to write
+    a.from = from;
+    a.count = count;
+    const uintptr_t oa = reinterpret_cast<uintptr_t>(out);
+    a.out = reinterpret_cast<uint8_t*>(oa & ~uintptr_t(15));
+    a.origin = oa & 15;
+    return run(c, ONC_K_DEFRAG_COPY, "gather_copy", [&] { return onc::launch_gather_copy(a, c->stream); });
+}
+
 int32_t onc_expected_message_len(const uint8_t* data, uint64_t len, uint32_t* out) {
     if (out) *out = 0;
     if (!data || len < 4) return ONC_ERR_INCOMPLETE_HEADER;          // rpc_message.rs:344-346

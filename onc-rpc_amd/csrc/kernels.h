@@ -12,6 +12,7 @@
 #include "defrag_plan.h"
 #include "fragment_iov_plan.h"
 #include "fragment_plan.h"
+#include "gather_plan.h"
 
 namespace onc {
 
@@ -220,6 +221,24 @@ struct FragmentIovArgs {
     uint64_t* info;             // [0] first piece of the first record beyond a capacity
 };
 
+// onc_piece_offsets / onc_gather_pieces (gather.hip). Scratch: the block
+// sums of the offsets (24 bytes per 256 pieces), in onc_defragment's buffer;
+// the copy uses none.
+struct GatherArgs {
+    const onc_frag_piece* pieces;   // npieces, 16-byte aligned
+    uint64_t npieces;
+    const uint8_t* base0;       // the sources, by ONC_PIECE_*: never indexed, so they stay in scalar registers
+    const uint8_t* base1;
+    const uint8_t* base2;
+    uint64_t len0, len1, len2;  // their lengths in bytes
+    uint64_t* piece_pos;        // npieces + 1: written by the offsets, read by the copy
+    uint64_t* result;           // [3] (the offsets)
+    GatherAgg* blk;             // per 256 pieces (+ 1: the whole list) (the offsets)
+    uint64_t from, count;       // the window of the stream (the copy)
+    uint8_t* out;               // the 16-byte aligned address at or below the caller's out
+    uint64_t origin;            // the caller's out from there (0..15)
+};
+
 struct DecArgs {
     uint64_t n;
     const uint8_t* wire;
@@ -371,6 +390,12 @@ hipError_t launch_fragiov_blk(const FragmentIovArgs& a, hipStream_t s);
 hipError_t launch_fragiov_blkscan(const FragmentIovArgs& a, hipStream_t s);
 hipError_t launch_fragiov_apply(const FragmentIovArgs& a, hipStream_t s);
 hipError_t launch_fragiov_fill(const FragmentIovArgs& a, hipStream_t s);
+// gather.hip
+hipError_t launch_gath_blk(const GatherArgs& a, hipStream_t s);
+hipError_t launch_gath_blkscan(const GatherArgs& a, hipStream_t s);
+hipError_t launch_gath_apply(const GatherArgs& a, hipStream_t s);
+hipError_t launch_gath_empty(const GatherArgs& a, hipStream_t s);
+hipError_t launch_gather_copy(const GatherArgs& a, hipStream_t s);
 // streams.hip
 hipError_t launch_streams_chase(const StreamsArgs& a, hipStream_t s);
 hipError_t launch_streams_write(const StreamsArgs& a, hipStream_t s);

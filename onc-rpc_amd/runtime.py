@@ -45,6 +45,7 @@ EXPORTED = [
     "onc_fragment", "onc_fragment_iov",
     "onc_frame_fragment_streams", "onc_defragment_extents",
     "onc_defragment_heads", "onc_decode_heads",
+    "onc_piece_offsets", "onc_gather_pieces",
 ]
 
 # onc_codec_options (include/onc_rpc.h)
@@ -71,6 +72,11 @@ class OncCodecOptions(C.Structure):
 class OncDecoded(C.Structure):
     _fields_ = [("msgs", C.c_void_p), ("unix_params", C.c_void_p), ("status", C.c_void_p),
                 ("aux0", C.c_void_p), ("aux1", C.c_void_p)]
+
+
+class OncGatherSrc(C.Structure):
+    """onc_gather_src: the three sources of a piece list, by ONC_PIECE_*."""
+    _fields_ = [("base", C.c_void_p * 3), ("len", C.c_uint64 * 3)]
 
 
 class CodecError(RuntimeError):
@@ -134,6 +140,8 @@ def load_library(path=LIB_PATH):
     lib.onc_defragment_extents.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, vp, vp]
     lib.onc_defragment_heads.argtypes = [vp, vp, vp, vp, u64, C.c_uint32, vp, u64, vp, vp, vp, vp, vp]
     lib.onc_decode_heads.argtypes = [vp, vp, C.c_uint32, vp, u64, i32, C.POINTER(OncDecoded)]
+    lib.onc_piece_offsets.argtypes = [vp, vp, u64, C.POINTER(OncGatherSrc), vp, vp]
+    lib.onc_gather_pieces.argtypes = [vp, vp, vp, u64, C.POINTER(OncGatherSrc), u64, u64, vp]
     for name in EXPORTED:
         getattr(lib, name).restype = getattr(lib, name).restype or i32
     # a stale library would read a differently laid out onc_batch and label
@@ -353,6 +361,21 @@ class Codec:
         self._check(self.lib.onc_fragment_iov(self.h, _ptr(iov), n, max_frag, _ptr(rec_max_frag), mp, mcap, pp, pcap,
                                               _ptr(out_off), _ptr(piece_off), _ptr(status), _ptr(result)),
                     "onc_fragment_iov")
+
+    def piece_offsets(self, pieces, npieces, src, piece_pos, result):
+        """onc_piece_offsets: where every piece of the list starts in the
+        stream (piece_pos = npieces + 1 words) and result = {stream bytes, bad
+        pieces, first bad piece}. `src`: gather_src(marks, hdr, payload)."""
+        self._check(self.lib.onc_piece_offsets(self.h, _ptr(pieces), npieces, C.byref(src), _ptr(piece_pos),
+                                               _ptr(result)), "onc_piece_offsets")
+
+    def gather_pieces(self, pieces, piece_pos, npieces, src, start, count, out):
+        """onc_gather_pieces: stream bytes [start, start + count) of the piece
+        list into `out` (any byte address: a tensor or an int device pointer,
+        device or mapped host memory)."""
+        optr = C.c_void_p(out) if isinstance(out, int) else _ptr(out)
+        self._check(self.lib.onc_gather_pieces(self.h, _ptr(pieces), _ptr(piece_pos), npieces, C.byref(src), start,
+                                               count, optr), "onc_gather_pieces")
 
     def frame_streams(self, wire, seg_off, seg_len, nseg, rec_start, rec_len, rec_seg, max_records, seg_result,
                       result):
@@ -917,6 +940,22 @@ def fragment_iov_host(codec: Codec, iov, max_frag, rec_max_frag=None, marks_cap=
             pieces.cpu().numpy()[:16 * max_pieces].view(L.FRAG_PIECE_DTYPE).copy(),
             out_off.cpu().numpy().view(np.uint64).copy(), piece_off.cpu().numpy().view(np.uint64).copy(),
             status.cpu().numpy()[:n].copy(), res.cpu().numpy().view(np.uint64).copy())
+
+
+def gather_src(*sources):
+    """onc_gather_src of up to three sources, in ONC_PIECE_* order: each a
+    uint8 tensor (its length is the tensor's), a (tensor or int device
+    pointer, length) pair, or None (NULL, length 0)."""
+    src = OncGatherSrc()
+    for k, s in enumerate(sources):
+        ln = None
+        if isinstance(s, tuple):
+            s, ln = s
+        if s is None:
+            continue
+        src.base[k] = s if isinstance(s, int) else s.data_ptr()
+        src.len[k] = s.numel() if ln is None else ln
+    return src
 
 
 def gather_pieces(pieces, marks, hdr, payload_arena):
