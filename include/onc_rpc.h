@@ -89,7 +89,10 @@ extern "C" {
  *    id: the one new outcome is a reason of ONC_DEC_BAD_EXTENT,
  *    ONC_EXTENT_HEAD_SHORT; onc_piece_offsets and onc_gather_pieces with
  *    onc_gather_src (a piece list written as one stream on the device), which
- *    add no status code and reuse onc_defragment's timing ids. */
+ *    add no status code and reuse onc_defragment's timing ids;
+ *    onc_payload_slots and onc_place_payloads (decoded payloads placed in
+ *    aligned slots on the device), which add no status code and reuse
+ *    onc_defragment's timing ids. */
 #define ONC_RPC_ABI_VERSION 8
 
 /* ------------------------------------------------------------------------ */
@@ -450,7 +453,9 @@ int onc_codec_sync(onc_codec* codec);
  * segment). onc_defragment_extents is covered as onc_defragment is, and
  * onc_frame_fragment_streams of up to max_records segments as
  * onc_frame_streams is (the two share one buffer of under 112 bytes per
- * segment). */
+ * segment). onc_payload_slots of up to max_records records keeps its block
+ * sums in onc_defragment's buffer (under 1 byte per record) and is covered
+ * too; onc_place_payloads needs no scratch. */
 int onc_codec_reserve(onc_codec* codec, uint64_t max_records);
 /* Map a caller's host buffer (a socket buffer: any malloc'd or mmap'd
  * range) for the kernels, so that an encode / decode reads and writes it in
@@ -519,7 +524,10 @@ int onc_abi_version(void);
  * onc_defragment_heads reports its plan launches (defrag_blk, defrag_blkscan,
  * defrag_frag, heads_place) under ONC_K_DEFRAG_PLAN and its gather
  * (heads_gather) under ONC_K_DEFRAG_COPY; it launches no onc_scan_lengths
- * kernel. onc_decode_heads reports under ONC_K_DEC_PARSE. */
+ * kernel. onc_decode_heads reports under ONC_K_DEC_PARSE. onc_payload_slots
+ * reports its launches (pay_blk, pay_blkscan, pay_apply; pay_empty) under
+ * ONC_K_DEFRAG_PLAN and onc_place_payloads its copy (place_copy) under
+ * ONC_K_DEFRAG_COPY. */
 #define ONC_K_ENC_LEN      0
 #define ONC_K_SCAN_TILES   1
 #define ONC_K_ENC_EMIT     2
@@ -1260,6 +1268,123 @@ int onc_piece_offsets(onc_codec* codec, const onc_frag_piece* pieces, uint64_t n
 int onc_gather_pieces(onc_codec* codec, const onc_frag_piece* pieces, const uint64_t* piece_pos,
                       uint64_t npieces, const onc_gather_src* src /*host*/,
                       uint64_t from, uint64_t count, uint8_t* out);
+
+/* Decoded payloads placed in aligned slots on the device: the receive-side
+ * counterpart of onc_gather_pieces. After onc_defragment_heads +
+ * onc_decode_heads every payload still lies scattered over its record's
+ * fragments in the caller's receive slab, and after onc_frame_streams +
+ * onc_decode_extents at an arbitrary byte address of it; these two calls move
+ * each payload byte exactly once, from where it arrived to an aligned slot of
+ * a caller's buffer (an NFS WRITE body for storage, the arguments of a GPU
+ * kernel), after which the slab can be reused. A decoded batch then re-encodes
+ * with msgs_out as the descriptors, auth_arena = the heads (or the wire) and
+ * payload_arena = the placed buffer.
+ *
+ * onc_payload_slots: where each decoded record's payload is, and where it
+ * goes. The result is exactly that of
+ *
+ *   off = k = bytes = 0
+ *   for r in 0 .. n-1:
+ *       m = msgs[r]
+ *       has = status[r] == ONC_OK and m.payload_len > 0 and
+ *             (m.msg_type == ONC_MSG_CALL or
+ *              (m.msg_type == ONC_MSG_REPLY and m.reply_stat == ONC_REPLY_ACCEPTED and m.stat == ONC_ACCEPT_SUCCESS))
+ *       base = rec_start ? rec_start[r] : r * head_len      # onc_decode_extents' offsets | onc_decode_heads'
+ *       pay_pos[r] = has ? u32(m.payload_off - base) : 0    # position in the record, mark included (>= 4)
+ *       pay_len[r] = has ? m.payload_len : 0
+ *       slot_off[r] = off
+ *       if msgs_out: msgs_out[r] = m, with payload_off = off when has
+ *       off += round_up(pay_len[r], align); k += has; bytes += pay_len[r]
+ *   slot_off[n] = off; result = {k, bytes, off}
+ *
+ *   msgs, status[dev, n]: a decode's descriptors and statuses. The payload
+ *                     words of a record that is not OK, or of a message kind
+ *                     that carries no payload, are ignored.
+ *   rec_start[dev, n]: the extents onc_decode_extents decoded; NULL: the heads
+ *                     form, record r's offsets count from r * head_len
+ *                     (head_len as in onc_decode_heads: a multiple of 16 in
+ *                     [64, 4096]). head_len is ignored with rec_start.
+ *   align           : a power of two in [1, 2^20]; every slot starts at a
+ *                     multiple of it.
+ *   msgs_out[dev, n]: optional; may be msgs itself.
+ *   result[dev, 3]  : {records with a payload, payload bytes, the capacity
+ *                     the destination needs (= slot_off[n])}.
+ *  - ONC_RC_EINVAL: a NULL codec, result or slot_off, an align that is not a
+ *    power of two in [1, 2^20], or (with rec_start NULL) a bad head_len,
+ *    whatever n is; with n > 0 a NULL msgs, status, pay_pos or pay_len.
+ *    ONC_RC_EALIGN: msgs or msgs_out not 16-byte aligned, slot_off not 8-byte
+ *    aligned. n == 0 gives slot_off[0] = 0 and a zero result.
+ *
+ * onc_place_payloads: the copy. The result is exactly that of
+ *
+ *   for r in 0 .. n-1:
+ *       if pay_len[r] == 0: continue
+ *       ok = pay_pos[r] >= 4 and pay_pos[r] <= rec_len[r] and pay_len[r] <= rec_len[r] - pay_pos[r]
+ *            and slot_off[r] <= dst_cap and pay_len[r] <= dst_cap - slot_off[r]     # no sum is formed
+ *       if not ok: continue                                  # never read, nothing written
+ *       for i in 0 .. pay_len[r]-1:
+ *           x = pay_pos[r] - 4 + i
+ *           j = rec_frag ? the last j in [rec_frag[r], rec_frag[r+1]) with frag_pre[j] <= x : r
+ *           pre = rec_frag ? frag_pre[j] : 0
+ *           dst[slot_off[r] + i] = wire[frag_start[j] + 4 + (x - pre)]
+ *
+ *   frag_start, frag_len[dev, nfrag]: onc_defragment_heads' inputs (the
+ *                     caller's own extents, trusted); rec_frag[dev, n + 1],
+ *                     frag_pre[dev, nfrag] and rec_len[dev, n] its outputs.
+ *                     The identity form, rec_frag = frag_pre = NULL: record r
+ *                     is fragment r — frag_start, frag_len and rec_len are
+ *                     onc_frame_streams' rec_start, rec_len and rec_len again
+ *                     (nfrag >= n).
+ *   pay_pos, pay_len[dev, n]: any slice of the record's body, not only the
+ *                     whole payload (the data of an NFS WRITE behind its
+ *                     arguments), which is why it is checked against the
+ *                     record.
+ *   slot_off[dev, n]: trusted as piece_pos is in onc_gather_pieces: it is
+ *                     non-decreasing, and slot_off[r] + pay_len[r] <=
+ *                     slot_off[r+1] wherever pay_len[r] > 0 — what
+ *                     onc_payload_slots writes; a caller's own list may leave
+ *                     larger gaps. (slot_off[n] is not read.)
+ *   dst[dev]        : any byte address, device memory or mapped host memory;
+ *                     must not overlap the wire or any of the arrays. No byte
+ *                     of dst is written outside the slices of OK records: the
+ *                     padding between slots, the bytes before dst and those at
+ *                     or after dst + dst_cap stay as they were.
+ * Source reads follow onc_decode's rule: only whole aligned 16-byte granules
+ * that hold bytes that are copied; no byte of a record outside its slice is
+ * read and nothing of a skipped record.
+ *  - ONC_RC_EINVAL: a NULL codec; a NULL rec_frag with a non-NULL frag_pre or
+ *    the reverse; the identity form with nfrag < n; with n > 0 a NULL wire,
+ *    frag_start, frag_len, rec_len, pay_pos, pay_len, slot_off or dst.
+ *    n == 0 launches nothing.
+ * Both calls are asynchronous on the codec's stream and every step is a kernel
+ * launch (no memset or memcpy node in a captured call). Scratch:
+ * onc_payload_slots keeps its block sums (24 bytes per 256 records: under 1
+ * byte per record) in onc_defragment's buffer: onc_codec_reserve(max_records
+ * >= n) covers it; growing it inside a capture is ONC_RC_ECAPTURE.
+ * onc_place_payloads uses none. The slots' launches report under
+ * ONC_K_DEFRAG_PLAN and the copy under ONC_K_DEFRAG_COPY.
+ * Kernels (payload.hip): onc_fragment's plan shape (block sums, one-workgroup
+ * scan, apply) over {slot bytes, records, payload bytes}, and
+ * onc_gather_pieces' copy with one more level of lookup: partitioned by the
+ * bytes of dst (a wave per 8 KiB tile), the records reaching into a tile
+ * staged in LDS, the fragment of a body byte found by binary search of
+ * frag_pre. All index arithmetic is 64-bit: frag_start, slot_off and the
+ * extent of dst may exceed 2^32. */
+int onc_payload_slots(onc_codec* codec, const onc_msg* msgs, const int32_t* status, uint64_t n,
+                      uint32_t head_len, const uint64_t* rec_start /* NULL: the heads form */,
+                      uint32_t align,
+                      uint32_t* pay_pos  /*[dev, n]*/, uint32_t* pay_len /*[dev, n]*/,
+                      uint64_t* slot_off /*[dev, n + 1]*/,
+                      onc_msg* msgs_out  /*[dev, n], optional; may be msgs itself*/,
+                      uint64_t* result   /*[dev, 3]*/);
+
+int onc_place_payloads(onc_codec* codec, const uint8_t* wire,
+                       const uint64_t* frag_start, const uint32_t* frag_len, uint64_t nfrag,
+                       const uint64_t* rec_frag /*[dev, n + 1]; NULL: record r is fragment r*/,
+                       const uint64_t* frag_pre /*[dev, nfrag]; NULL with rec_frag NULL*/,
+                       const uint32_t* rec_len  /*[dev, n]*/,
+                       const uint32_t* pay_pos, const uint32_t* pay_len, const uint64_t* slot_off, uint64_t n,
+                       uint8_t* dst, uint64_t dst_cap);
 
 /* Exclusive scan of record lengths into offsets:
  * rec_off[0] = base, rec_off[i+1] = rec_off[i] + rec_len[i]  ([dev]). */

@@ -1844,14 +1844,165 @@ inline ReassembledHeads reassemble_heads(Codec& codec, const uint8_t* wire, size
 // and machine names; its own payload view covers only the payload bytes that
 // lie inside the head. The whole payload is payload_pieces(r) — slices of the
 // caller's wire, nothing copied — or payload(r), a gathered copy.
+// What place_payloads returns: every decoded payload in an aligned slot of one
+// device buffer (onc_payload_slots + onc_place_payloads), each payload byte
+// moved once from where it arrived. Everything here is device memory, owned by
+// this object (one hipMalloc, freed with it): record r's payload is
+// views[r].len bytes at the device address views[r].ptr = dev + slot_off[r],
+// a multiple of `align` from dev. fetch() copies one back for a look at it.
+struct PlacedPayloads {
+    uint8_t* dev = nullptr;                // the placed bytes: `bytes` of them
+    uint64_t* slot_off_dev = nullptr;      // n + 1 words behind them
+    uint64_t bytes = 0;                    // the capacity the slots need (slot_off[n])
+    uint32_t align = 1;
+    size_t n_payloads = 0;                 // records with a payload
+    uint64_t payload_bytes = 0;            // their bytes, unpadded
+    std::vector<uint64_t> slot_off;        // n + 1 (a host copy)
+    std::vector<Bytes> views;              // n: device addresses; empty for a record without a payload
+
+    PlacedPayloads() = default;
+    PlacedPayloads(const PlacedPayloads&) = delete;
+    PlacedPayloads& operator=(const PlacedPayloads&) = delete;
+    PlacedPayloads(PlacedPayloads&& o) noexcept { *this = std::move(o); }
+    PlacedPayloads& operator=(PlacedPayloads&& o) noexcept {
+        if (this != &o) {
+            if (dev) (void)hipFree(dev);
+            dev = o.dev;
+            slot_off_dev = o.slot_off_dev;
+            bytes = o.bytes;
+            align = o.align;
+            n_payloads = o.n_payloads;
+            payload_bytes = o.payload_bytes;
+            slot_off = std::move(o.slot_off);
+            views = std::move(o.views);
+            o.dev = nullptr;
+            o.slot_off_dev = nullptr;
+        }
+        return *this;
+    }
+    ~PlacedPayloads() {
+        if (dev) (void)hipFree(dev);
+    }
+    std::vector<uint8_t> fetch(size_t r) const {
+        std::vector<uint8_t> out(views[r].len);
+        if (!out.empty())
+            detail::hip_check(hipMemcpy(out.data(), views[r].ptr, out.size(), hipMemcpyDeviceToHost), "hipMemcpy(payload)");
+        return out;
+    }
+};
+
+namespace detail {
+
+// Where a slab's records lie for onc_place_payloads: the heads form
+// (rec_frag / frag_pre set) or the identity form (both null: record r is
+// fragment r).
+struct PlaceSource {
+    const uint8_t* wire;
+    size_t wire_len;
+    const uint64_t* frag_start;
+    const uint32_t* frag_len;
+    size_t nfrag;
+    const uint64_t* rec_frag;      // n + 1, or null
+    const uint64_t* frag_pre;      // nfrag, or null
+    const uint32_t* rec_len;       // n
+    const uint64_t* rec_start;     // n: onc_payload_slots' rec_start form, or null: the heads form
+    uint32_t head_len;
+};
+
+// onc_payload_slots + onc_place_payloads of n decoded records, inputs through
+// the stage, outputs in one device allocation; one synchronisation.
+inline PlacedPayloads place_decoded(Codec& codec, const PlaceSource& s, const onc_msg* msgs, const int32_t* status,
+                                    size_t n, uint32_t align) {
+    PlacedPayloads p;
+    p.align = align;
+    p.slot_off.assign(n + 1, 0);
+    p.views.assign(n, Bytes());
+    if (align == 0 || align > (1u << 20) || (align & (align - 1))) throw CodecError("place_payloads: align");
+    if (!n) return p;
+    // the capacity is known here too (the device computes the same sum)
+    uint64_t cap = 0;
+    for (size_t r = 0; r < n; ++r) {
+        const onc_msg& m = msgs[r];
+        const bool has = status[r] == ONC_OK && m.payload_len &&
+                         (m.msg_type == ONC_MSG_CALL || (m.msg_type == ONC_MSG_REPLY && m.reply_stat == ONC_REPLY_ACCEPTED &&
+                                                         m.stat == ONC_ACCEPT_SUCCESS));
+        if (has) cap += (uint64_t(m.payload_len) + align - 1) & ~uint64_t(align - 1);
+    }
+    const size_t off_at = size_t((cap + 15) & ~uint64_t(15));
+    void* d = nullptr;
+    hip_check(hipMalloc(&d, off_at + 8 * (n + 1) + 16), "hipMalloc(placed payloads)");
+    p.dev = static_cast<uint8_t*>(d);
+    p.slot_off_dev = reinterpret_cast<uint64_t*>(p.dev + off_at);
+    const bool heads = s.rec_frag != nullptr;
+    Carve c{codec.stage(need<uint8_t>(s.wire_len) + need<uint64_t>(s.nfrag) + need<uint32_t>(s.nfrag) +
+                        2 * need<uint64_t>(s.nfrag + 1) + need<uint64_t>(n) + 3 * need<uint32_t>(n) + need<onc_msg>(n) +
+                        need<int32_t>(n) + need<uint64_t>(3))};
+    const auto w = c.take<uint8_t>(s.wire_len);
+    if (s.wire_len) std::memcpy(w.host, s.wire, s.wire_len);
+    const auto fs = c.take<uint64_t>(s.nfrag);
+    const auto fl = c.take<uint32_t>(s.nfrag);
+    const auto rf = c.take<uint64_t>(s.nfrag + 1);
+    const auto fp = c.take<uint64_t>(s.nfrag + 1);
+    const auto rs = c.take<uint64_t>(n);
+    const auto rl = c.take<uint32_t>(n);
+    const auto pp = c.take<uint32_t>(n);
+    const auto pl = c.take<uint32_t>(n);
+    const auto dm = c.take<onc_msg>(n);
+    const auto st = c.take<int32_t>(n);
+    const auto res = c.take<uint64_t>(3);
+    std::memcpy(fs.host, s.frag_start, 8 * s.nfrag);
+    std::memcpy(fl.host, s.frag_len, 4 * s.nfrag);
+    if (heads) {
+        std::memcpy(rf.host, s.rec_frag, 8 * (n + 1));
+        std::memcpy(fp.host, s.frag_pre, 8 * s.nfrag);
+    }
+    if (s.rec_start) std::memcpy(rs.host, s.rec_start, 8 * n);
+    std::memcpy(rl.host, s.rec_len, 4 * n);
+    std::memcpy(dm.host, msgs, sizeof(onc_msg) * n);
+    std::memcpy(st.host, status, 4 * n);
+    codec.check(onc_payload_slots(codec.get(), dm.dev, st.dev, n, s.head_len, s.rec_start ? rs.dev : nullptr, align,
+                                  pp.dev, pl.dev, p.slot_off_dev, nullptr, res.dev),
+                "onc_payload_slots");
+    codec.check(onc_place_payloads(codec.get(), w.dev, fs.dev, fl.dev, s.nfrag, heads ? rf.dev : nullptr,
+                                   heads ? fp.dev : nullptr, rl.dev, pp.dev, pl.dev, p.slot_off_dev, n, p.dev, cap),
+                "onc_place_payloads");
+    codec.sync();
+    hip_check(hipMemcpy(p.slot_off.data(), p.slot_off_dev, 8 * (n + 1), hipMemcpyDeviceToHost), "hipMemcpy(slot_off)");
+    p.n_payloads = size_t(res.host[0]);
+    p.payload_bytes = res.host[1];
+    p.bytes = res.host[2];
+    if (p.bytes != cap || p.slot_off[n] != cap) throw CodecError("place_payloads: capacities differ");
+    for (size_t r = 0; r < n; ++r)
+        if (pl.host[r]) p.views[r] = Bytes(p.dev + p.slot_off[r], pl.host[r]);
+    return p;
+}
+
+}  // namespace detail
+
 struct FragmentedHeads {
     std::vector<Decoded> results;
     std::vector<SegmentRecords> segments;
     ReassembledHeads heads;
     std::vector<uint64_t> payload_pos;     // per record: where its payload starts in the record (0: none)
     std::vector<uint64_t> payload_len;     // per record: its true length
+    std::vector<onc_msg> descriptors;      // per record: as onc_decode_heads wrote it (offsets count from heads.heads)
+    std::vector<int32_t> status;           // per record: its decode status
     const uint8_t* wire = nullptr;
     bool retried = false;                  // a header did not fit head_len: decoded from 736-byte heads
+
+    // Every payload gathered from its fragments into an `align`-aligned slot
+    // of one device buffer, on the device (onc_payload_slots +
+    // onc_place_payloads; payload(r) below walks the fragments on the host).
+    PlacedPayloads place_payloads(Codec& codec, uint32_t align = 16) const {
+        const size_t nfrag = heads.n_frags();
+        size_t wire_len = 0;
+        for (size_t j = 0; j < nfrag; ++j)
+            wire_len = std::max<size_t>(wire_len, size_t(heads.frag_start[j] + heads.frag_len[j]));
+        const detail::PlaceSource s{wire, wire_len, heads.frag_start.data(), heads.frag_len.data(), nfrag,
+                                    heads.rec_frag.data(), heads.frag_pre.data(), heads.rec_len.data(), nullptr,
+                                    heads.head_len};
+        return detail::place_decoded(codec, s, descriptors.data(), status.data(), descriptors.size(), align);
+    }
 
     std::vector<Bytes> payload_pieces(size_t r) const {
         if (!payload_len[r]) return {};
@@ -1864,6 +2015,42 @@ struct FragmentedHeads {
         return out;
     }
 };
+
+// The same for records decoded where they lie — try_from_streams' results (or
+// try_from_stream's, try_from's), whose payload views point into the caller's
+// `wire` at arbitrary byte addresses: every payload moved once into an
+// `align`-aligned slot of one device buffer, after which the wire can be
+// reused (onc_payload_slots' rec_start form + onc_place_payloads' identity
+// form; a record is described by its payload's extent alone).
+inline PlacedPayloads place_payloads(Codec& codec, const uint8_t* wire, size_t wire_len,
+                                     const std::vector<Decoded>& results, uint32_t align = 16) {
+    const size_t n = results.size();
+    std::vector<onc_msg> msgs(n);
+    std::vector<int32_t> status(n);
+    std::vector<uint64_t> start(n, 0);
+    std::vector<uint32_t> len(n, 4);
+    for (size_t r = 0; r < n; ++r) {
+        std::memset(&msgs[r], 0, sizeof(onc_msg));
+        status[r] = results[r].status;
+        if (!results[r].ok()) continue;
+        const RpcMessage& m = *results[r].message;
+        Bytes p;
+        if (const CallBody* cb = m.call_body()) {
+            p = cb->payload();
+        } else if (const AcceptedReply* a = m.reply_body()->accepted()) {
+            if (a->status().kind() == AcceptedStatus::Kind::Success) p = a->status().payload();
+        }
+        if (!p.len) continue;
+        if (p.ptr < wire + 4 || p.ptr + p.len > wire + wire_len) throw CodecError("place_payloads: a payload outside the wire");
+        msgs[r].msg_type = ONC_MSG_CALL;
+        msgs[r].payload_len = uint32_t(p.len);
+        msgs[r].payload_off = uint64_t(p.ptr - wire);
+        start[r] = msgs[r].payload_off - 4;                  // the four bytes before it stand for a mark: never read
+        len[r] = uint32_t(p.len) + 4;
+    }
+    const detail::PlaceSource s{wire, wire_len, start.data(), len.data(), n, nullptr, nullptr, len.data(), start.data(), 0};
+    return detail::place_decoded(codec, s, msgs.data(), status.data(), n, align);
+}
 
 inline FragmentedHeads BatchDecoder::try_from_fragmented_heads(Codec& codec, const uint8_t* wire, size_t wire_len,
                                                                const std::vector<Segment>& segments, DecodeMode mode,
@@ -1896,6 +2083,8 @@ inline FragmentedHeads BatchDecoder::try_from_fragmented_heads(Codec& codec, con
             f.retried = true;
             continue;
         }
+        f.descriptors.assign(o.msgs.host, o.msgs.host + n);
+        f.status.assign(o.status.host, o.status.host + n);
         // the messages' own payload views end with the head
         for (size_t i = 0; i < n; ++i) {
             if (o.status.host[i] != ONC_OK) continue;

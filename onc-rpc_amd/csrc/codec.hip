@@ -1644,6 +1644,71 @@ int onc_gather_pieces(onc_codec* c, const onc_frag_piece* pieces, const uint64_t
     return run(c, ONC_K_DEFRAG_COPY, "gather_copy", [&] { return onc::launch_gather_copy(a, c->stream); });
 }
 
+int onc_payload_slots(onc_codec* c, const onc_msg* msgs, const int32_t* status, uint64_t n, uint32_t head_len,
+                      const uint64_t* rec_start, uint32_t align, uint32_t* pay_pos, uint32_t* pay_len,
+                      uint64_t* slot_off, onc_msg* msgs_out, uint64_t* result) {
+    if (!c || !result || !slot_off || !onc::payload_align_ok(align)) return ONC_RC_EINVAL;
+    if (!rec_start && !onc::heads_len_ok(head_len)) return ONC_RC_EINVAL;
+    if (n && (!msgs || !status || !pay_pos || !pay_len)) return ONC_RC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(msgs) & 15) || (reinterpret_cast<uintptr_t>(msgs_out) & 15) ||
+        (reinterpret_cast<uintptr_t>(slot_off) & 7))
+        return ONC_RC_EALIGN;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    onc::PaySlotsArgs a{};
+    a.msgs = msgs;
+    a.status = status;
+    a.n = n;
+    a.head_len = head_len;
+    a.rec_start = rec_start;
+    a.align = align;
+    a.pay_pos = pay_pos;
+    a.pay_len = pay_len;
+    a.slot_off = slot_off;
+    a.msgs_out = msgs_out;
+    a.result = result;
+    if (n == 0) return run(c, ONC_K_DEFRAG_PLAN, "pay_empty", [&] { return onc::launch_pay_empty(a, c->stream); });
+    // onc_defragment's buffer, a record where it keeps a fragment: the block
+    // sums alone (24 (n / 256 + 2) bytes of its 28 per fragment)
+    int rc = ensure_defrag(c, n);
+    if (rc != ONC_RC_OK) return rc;
+    a.blk = reinterpret_cast<onc::PayAgg*>(c->dfr);
+    static_assert(sizeof(onc::PayAgg) == 24, "the block sums fit the first array: 24 (F / 256 + 2) <= 8 (F + 2)");
+    rc = run(c, ONC_K_DEFRAG_PLAN, "pay_blk", [&] { return onc::launch_pay_blk(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "pay_blkscan", [&] { return onc::launch_pay_blkscan(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "pay_apply", [&] { return onc::launch_pay_apply(a, c->stream); });
+    return rc;
+}
+
+int onc_place_payloads(onc_codec* c, const uint8_t* wire, const uint64_t* frag_start, const uint32_t* frag_len,
+                       uint64_t nfrag, const uint64_t* rec_frag, const uint64_t* frag_pre, const uint32_t* rec_len,
+                       const uint32_t* pay_pos, const uint32_t* pay_len, const uint64_t* slot_off, uint64_t n,
+                       uint8_t* dst, uint64_t dst_cap) {
+    if (!c || (rec_frag == nullptr) != (frag_pre == nullptr)) return ONC_RC_EINVAL;
+    if (n && (!wire || !frag_start || !frag_len || !rec_len || !pay_pos || !pay_len || !slot_off || !dst))
+        return ONC_RC_EINVAL;
+    if (!rec_frag && nfrag < n) return ONC_RC_EINVAL;       // record r is fragment r
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    if (n == 0 || dst_cap == 0) return ONC_RC_OK;           // nothing to write
+    onc::PlaceArgs a{};
+    a.wire = wire;
+    a.frag_start = frag_start;
+    a.frag_len = frag_len;
+    a.rec_frag = rec_frag;
+    a.frag_pre = frag_pre;
+    a.rec_len = rec_len;
+    a.pay_pos = pay_pos;
+    a.pay_len = pay_len;
+    a.slot_off = slot_off;
+    a.n = n;
+    const uintptr_t da = reinterpret_cast<uintptr_t>(dst);
+    a.out = reinterpret_cast<uint8_t*>(da & ~uintptr_t(15));
+    a.origin = da & 15;
+    a.dst_cap = dst_cap;
+    return run(c, ONC_K_DEFRAG_COPY, "place_copy", [&] { return onc::launch_place_copy(a, c->stream); });
+}
+
 int32_t onc_expected_message_len(const uint8_t* data, uint64_t len, uint32_t* out) {
     if (out) *out = 0;
     if (!data || len < 4) return ONC_ERR_INCOMPLETE_HEADER;          // rpc_message.rs:344-346

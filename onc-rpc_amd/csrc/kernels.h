@@ -13,6 +13,7 @@
 #include "fragment_iov_plan.h"
 #include "fragment_plan.h"
 #include "gather_plan.h"
+#include "payload_plan.h"
 
 namespace onc {
 
@@ -239,6 +240,40 @@ struct GatherArgs {
     uint64_t origin;            // the caller's out from there (0..15)
 };
 
+// onc_payload_slots (payload.hip). Scratch: the block sums of the slots (24
+// bytes per 256 records), in onc_defragment's buffer.
+struct PaySlotsArgs {
+    const onc_msg* msgs;        // n, 16-byte aligned
+    const int32_t* status;      // n
+    uint64_t n;
+    uint32_t head_len;          // the heads form: record r's offsets count from r * head_len
+    const uint64_t* rec_start;  // n, or NULL: the heads form
+    uint32_t align;             // a power of two in [1, 2^20]
+    uint32_t* pay_pos;          // n
+    uint32_t* pay_len;          // n
+    uint64_t* slot_off;         // n + 1
+    onc_msg* msgs_out;          // n, optional; may be msgs
+    uint64_t* result;           // [3]
+    PayAgg* blk;                // per 256 records (+ 1: the whole batch)
+};
+
+// onc_place_payloads (payload.hip). No scratch.
+struct PlaceArgs {
+    const uint8_t* wire;
+    const uint64_t* frag_start; // nfrag
+    const uint32_t* frag_len;   // nfrag
+    const uint64_t* rec_frag;   // n + 1, or NULL: record r is fragment r
+    const uint64_t* frag_pre;   // nfrag, or NULL with rec_frag
+    const uint32_t* rec_len;    // n
+    const uint32_t* pay_pos;    // n
+    const uint32_t* pay_len;    // n
+    const uint64_t* slot_off;   // n
+    uint64_t n;
+    uint8_t* out;               // the 16-byte aligned address at or below the caller's dst
+    uint64_t origin;            // the caller's dst from there (0..15)
+    uint64_t dst_cap;           // the caller's capacity
+};
+
 struct DecArgs {
     uint64_t n;
     const uint8_t* wire;
@@ -396,6 +431,12 @@ hipError_t launch_gath_blkscan(const GatherArgs& a, hipStream_t s);
 hipError_t launch_gath_apply(const GatherArgs& a, hipStream_t s);
 hipError_t launch_gath_empty(const GatherArgs& a, hipStream_t s);
 hipError_t launch_gather_copy(const GatherArgs& a, hipStream_t s);
+// payload.hip
+hipError_t launch_pay_blk(const PaySlotsArgs& a, hipStream_t s);
+hipError_t launch_pay_blkscan(const PaySlotsArgs& a, hipStream_t s);
+hipError_t launch_pay_apply(const PaySlotsArgs& a, hipStream_t s);
+hipError_t launch_pay_empty(const PaySlotsArgs& a, hipStream_t s);
+hipError_t launch_place_copy(const PlaceArgs& a, hipStream_t s);
 // streams.hip
 hipError_t launch_streams_chase(const StreamsArgs& a, hipStream_t s);
 hipError_t launch_streams_write(const StreamsArgs& a, hipStream_t s);

@@ -46,6 +46,7 @@ EXPORTED = [
     "onc_frame_fragment_streams", "onc_defragment_extents",
     "onc_defragment_heads", "onc_decode_heads",
     "onc_piece_offsets", "onc_gather_pieces",
+    "onc_payload_slots", "onc_place_payloads",
 ]
 
 # onc_codec_options (include/onc_rpc.h)
@@ -142,6 +143,8 @@ def load_library(path=LIB_PATH):
     lib.onc_decode_heads.argtypes = [vp, vp, C.c_uint32, vp, u64, i32, C.POINTER(OncDecoded)]
     lib.onc_piece_offsets.argtypes = [vp, vp, u64, C.POINTER(OncGatherSrc), vp, vp]
     lib.onc_gather_pieces.argtypes = [vp, vp, vp, u64, C.POINTER(OncGatherSrc), u64, u64, vp]
+    lib.onc_payload_slots.argtypes = [vp, vp, vp, u64, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, vp]
+    lib.onc_place_payloads.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp, u64]
     for name in EXPORTED:
         getattr(lib, name).restype = getattr(lib, name).restype or i32
     # a stale library would read a differently laid out onc_batch and label
@@ -376,6 +379,30 @@ class Codec:
         optr = C.c_void_p(out) if isinstance(out, int) else _ptr(out)
         self._check(self.lib.onc_gather_pieces(self.h, _ptr(pieces), _ptr(piece_pos), npieces, C.byref(src), start,
                                                count, optr), "onc_gather_pieces")
+
+    def payload_slots(self, msgs, status, n, align, pay_pos, pay_len, slot_off, result, head_len=0, rec_start=None,
+                      msgs_out=None):
+        """onc_payload_slots: per decoded record where its payload is in the
+        record (pay_pos, pay_len) and the `align`-aligned slot it goes to
+        (slot_off = n + 1 words); result = {records with a payload, payload
+        bytes, destination bytes needed}. The heads form (head_len) unless
+        rec_start gives onc_decode_extents' offsets; msgs_out (may be msgs):
+        the descriptors with payload_off rebased to the slots."""
+        self._check(self.lib.onc_payload_slots(self.h, _ptr(msgs), _ptr(status), n, head_len, _ptr(rec_start), align,
+                                               _ptr(pay_pos), _ptr(pay_len), _ptr(slot_off), _ptr(msgs_out),
+                                               _ptr(result)), "onc_payload_slots")
+
+    def place_payloads(self, wire, frag_start, frag_len, nfrag, rec_frag, frag_pre, rec_len, pay_pos, pay_len,
+                       slot_off, n, dst, dst_cap=None):
+        """onc_place_payloads: every OK slice (pay_pos, pay_len) of record r,
+        gathered from its fragments, into dst[slot_off[r], +pay_len[r])
+        (`dst`: a tensor, or an int device pointer with dst_cap). rec_frag =
+        frag_pre = None: record r is fragment r."""
+        cap = dst.numel() if dst_cap is None else dst_cap
+        dptr = C.c_void_p(dst) if isinstance(dst, int) else _ptr(dst)
+        self._check(self.lib.onc_place_payloads(self.h, _ptr(wire), _ptr(frag_start), _ptr(frag_len), nfrag,
+                                                _ptr(rec_frag), _ptr(frag_pre), _ptr(rec_len), _ptr(pay_pos),
+                                                _ptr(pay_len), _ptr(slot_off), n, dptr, cap), "onc_place_payloads")
 
     def frame_streams(self, wire, seg_off, seg_len, nseg, rec_start, rec_len, rec_seg, max_records, seg_result,
                       result):
@@ -847,6 +874,77 @@ def decode_host_heads(codec: Codec, heads, head_len, rec_len, mode, device="cuda
                        bufs.aux1)
     codec.sync()
     return bufs.to_host()
+
+
+def _dev_words(arr, dtype, view, device, extra=1):
+    """A host array as a device tensor of `view` words, `extra` zero words behind it."""
+    torch = _torch()
+    a = np.ascontiguousarray(arr, dtype)
+    return torch.from_numpy(np.append(a, np.zeros(extra, dtype)).view(view).copy()).to(device)
+
+
+def payload_slots_host(codec: Codec, msgs, status, align, head_len=0, rec_start=None, msgs_out=None, extra=4,
+                       device="cuda"):
+    """Convenience: host descriptors (L.MSG_DTYPE) and statuses ->
+    onc_payload_slots -> a dict of host arrays: pay_pos[n], pay_len[n],
+    slot_off[n + 1], result[3], msgs_out[n] (None unless msgs_out is
+    "separate" or "inplace": written to msgs itself), and `raw`: the whole
+    output arrays with `extra` words behind them, pre-filled with sentinels
+    (-1; descriptors 0xA5), so that a caller can see what was left alone."""
+    torch = _torch()
+    m = np.ascontiguousarray(msgs, L.MSG_DTYPE)
+    n = len(m)
+    d_msgs = torch.full(((n + extra) * 64,), 0xA5, dtype=torch.uint8, device=device)
+    if n:
+        d_msgs[:n * 64] = torch.from_numpy(m.view(np.uint8).reshape(-1).copy()).to(device)
+    d_st = _dev_words(status, np.int32, np.int32, device)
+    d_rs = None if rec_start is None else _dev_words(rec_start, np.uint64, np.int64, device)
+    pay_pos = torch.full((n + extra,), -1, dtype=torch.int32, device=device)
+    pay_len = torch.full((n + extra,), -1, dtype=torch.int32, device=device)
+    slot_off = torch.full((n + 1 + extra,), -1, dtype=torch.int64, device=device)
+    res = torch.full((3 + extra,), -1, dtype=torch.int64, device=device)
+    d_out = None
+    if msgs_out == "separate":
+        d_out = torch.full(((n + extra) * 64,), 0xA5, dtype=torch.uint8, device=device)
+    elif msgs_out == "inplace":
+        d_out = d_msgs
+    codec.payload_slots(d_msgs, d_st, n, align, pay_pos, pay_len, slot_off, res, head_len=head_len, rec_start=d_rs,
+                        msgs_out=d_out)
+    codec.sync()
+    raw = {"pay_pos": pay_pos.cpu().numpy().view(np.uint32).copy(), "pay_len": pay_len.cpu().numpy().view(np.uint32).copy(),
+           "slot_off": slot_off.cpu().numpy().view(np.uint64).copy(), "result": res.cpu().numpy().view(np.uint64).copy(),
+           "msgs": d_msgs.cpu().numpy().copy(), "msgs_out": None if d_out is None else d_out.cpu().numpy().copy()}
+    return {"pay_pos": raw["pay_pos"][:n], "pay_len": raw["pay_len"][:n], "slot_off": raw["slot_off"][:n + 1],
+            "result": raw["result"][:3],
+            "msgs_out": None if d_out is None else raw["msgs_out"][:n * 64].view(L.MSG_DTYPE), "raw": raw}
+
+
+def place_payloads_host(codec: Codec, wire, frag_start, frag_len, rec_frag, frag_pre, rec_len, pay_pos, pay_len,
+                        slot_off, dst_cap, shift=0, fill=0xA5, guard=64, device="cuda"):
+    """Convenience: a host wire, its fragment extents, onc_defragment_heads'
+    rec_frag / frag_pre / rec_len (rec_frag = frag_pre = None: the identity
+    form) and the slices -> onc_place_payloads into a destination `shift`
+    bytes past a 16-byte boundary -> the `guard` bytes before dst, its dst_cap
+    bytes and the `guard` bytes behind them as one host array, `fill` where
+    nothing was written."""
+    torch = _torch()
+    n = len(pay_len)
+    w = to_device(np.frombuffer(bytes(wire) + b"\0" * 16, np.uint8), device)
+    d_fs = _dev_words(frag_start, np.uint64, np.int64, device)
+    d_fl = _dev_words(frag_len, np.uint32, np.int32, device)
+    d_rf = None if rec_frag is None else _dev_words(rec_frag, np.uint64, np.int64, device)
+    d_fp = None if frag_pre is None else _dev_words(frag_pre, np.uint64, np.int64, device)
+    d_rl = _dev_words(rec_len, np.uint32, np.int32, device)
+    d_pp = _dev_words(pay_pos, np.uint32, np.int32, device)
+    d_pl = _dev_words(pay_len, np.uint32, np.int32, device)
+    d_so = _dev_words(slot_off, np.uint64, np.int64, device)
+    assert guard % 16 == 0 and 0 <= shift < 16
+    base, lo = aligned_bytes(guard + dst_cap + guard + 16, fill, device)
+    at = lo + guard + shift
+    codec.place_payloads(w, d_fs, d_fl, len(frag_start), d_rf, d_fp, d_rl, d_pp, d_pl, d_so, n, base.data_ptr() + at,
+                         dst_cap=dst_cap)
+    codec.sync()
+    return base.cpu().numpy()[at - guard:at + dst_cap + guard].copy()
 
 
 def reassemble_host_stream(codec: Codec, buf: bytes, device="cuda"):
