@@ -92,7 +92,9 @@ extern "C" {
  *    add no status code and reuse onc_defragment's timing ids;
  *    onc_payload_slots and onc_place_payloads (decoded payloads placed in
  *    aligned slots on the device), which add no status code and reuse
- *    onc_defragment's timing ids. */
+ *    onc_defragment's timing ids; onc_route_calls with onc_route (decoded
+ *    Calls dispatched to handlers on the device), which adds no status code
+ *    and reuses onc_defragment's timing ids. */
 #define ONC_RPC_ABI_VERSION 8
 
 /* ------------------------------------------------------------------------ */
@@ -455,7 +457,11 @@ int onc_codec_sync(onc_codec* codec);
  * onc_frame_streams is (the two share one buffer of under 112 bytes per
  * segment). onc_payload_slots of up to max_records records keeps its block
  * sums in onc_defragment's buffer (under 1 byte per record) and is covered
- * too; onc_place_payloads needs no scratch. */
+ * too; onc_place_payloads needs no scratch. onc_route_calls of up to
+ * max_records records keeps its bin counts there as well (about 1 byte per
+ * record at 256 bins, and 2 KiB of them however few the records): that buffer
+ * is never smaller than 65536 fragments' worth (1.8 MB), so a reserve for a
+ * handful of records covers the call at any table and handler count. */
 int onc_codec_reserve(onc_codec* codec, uint64_t max_records);
 /* Map a caller's host buffer (a socket buffer: any malloc'd or mmap'd
  * range) for the kernels, so that an encode / decode reads and writes it in
@@ -527,7 +533,9 @@ int onc_abi_version(void);
  * kernel. onc_decode_heads reports under ONC_K_DEC_PARSE. onc_payload_slots
  * reports its launches (pay_blk, pay_blkscan, pay_apply; pay_empty) under
  * ONC_K_DEFRAG_PLAN and onc_place_payloads its copy (place_copy) under
- * ONC_K_DEFRAG_COPY. */
+ * ONC_K_DEFRAG_COPY. onc_route_calls reports its classify and scan launches
+ * (route_classify, route_scan_bins, route_scan_total) under
+ * ONC_K_DEFRAG_PLAN and its scatter (route_scatter) under ONC_K_DEFRAG_COPY. */
 #define ONC_K_ENC_LEN      0
 #define ONC_K_SCAN_TILES   1
 #define ONC_K_ENC_EMIT     2
@@ -1385,6 +1393,140 @@ int onc_place_payloads(onc_codec* codec, const uint8_t* wire,
                        const uint32_t* rec_len  /*[dev, n]*/,
                        const uint32_t* pay_pos, const uint32_t* pay_len, const uint64_t* slot_off, uint64_t n,
                        uint8_t* dst, uint64_t dst_cap);
+
+/* ------------------------------------------------------------------------ */
+/* Dispatch: decoded Calls to their handlers                                 */
+/* ------------------------------------------------------------------------ */
+
+/* A decode leaves n descriptors in arrival order: Calls of every program,
+ * version and procedure the peers chose to send, a client's Replies, failed
+ * records. Before any handler can run a server finds each Call's handler,
+ * hands every handler its Calls as one contiguous batch, and answers the Calls
+ * it does not serve as RFC 5531 §9 prescribes (the reference leaves that loop
+ * to the application: CallBody::program / program_version / procedure, and
+ * AcceptedStatus::ProgramUnavailable / ProgramMismatch{low, high} /
+ * ProcedureUnavailable, src/reply/accepted_reply.rs). onc_route_calls is that
+ * loop as one batch call on the device: it classifies every record against a
+ * small route table, groups the records stably by handler and writes the reply
+ * descriptors — complete for the Calls nobody serves, skeletons for the rest —
+ * in an order onc_encode takes directly. Credential checks (AUTH_ERROR
+ * rejections) and the matching of a client's Replies to its outstanding xids
+ * are not part of it.
+ *
+ * A route: the procedures [proc_first, proc_first + proc_count) of one
+ * (program, version). Procedure p goes to handler handler_first + (p -
+ * proc_first), or to handler_first for every p with ONC_ROUTE_ONE_HANDLER. */
+#define ONC_ROUTE_TABLE_MAX    1024u   /* entries */
+#define ONC_ROUTE_HANDLERS_MAX 253u    /* so that handlers + 3 special bins <= 256 */
+#define ONC_ROUTE_ONE_HANDLER  0x1u    /* flags: every procedure of the range goes to handler_first */
+
+typedef struct onc_route {            /* 24 bytes */
+    uint32_t program;
+    uint32_t version;
+    uint32_t proc_first;              /* procedures [proc_first, proc_first + proc_count) */
+    uint32_t proc_count;
+    uint32_t handler_first;
+    uint32_t flags;                   /* ONC_ROUTE_*; other bits must be 0 */
+} onc_route;
+
+/* The nh + 3 bins: handler h < nh holds the OK Calls routed to it; then */
+#define ONC_ROUTE_BIN_REJECTED(nh) ((uint32_t)(nh))        /* OK Calls that no route serves */
+#define ONC_ROUTE_BIN_NOT_CALL(nh) ((uint32_t)(nh) + 1u)   /* OK records whose msg_type != ONC_MSG_CALL */
+#define ONC_ROUTE_BIN_FAILED(nh)   ((uint32_t)(nh) + 2u)   /* records whose status != ONC_OK */
+#define ONC_ROUTE_TILE 1024u   /* records per workgroup of the kernels (tests: the sizes around it) */
+
+/* onc_route_calls. The result is exactly that of
+ *
+ *   valid(table): for every i:
+ *       proc_count >= 1
+ *       proc_first + proc_count <= 2^32
+ *       (flags & ~1) == 0
+ *       handler_first + (ONE_HANDLER ? 1 : proc_count) <= nh
+ *     and for every i + 1 < ntab:
+ *       (program, version, proc_first)[i] < [i+1] lexicographically, unsigned
+ *       with equal (program, version): proc_first[i] + proc_count[i] <= proc_first[i+1]
+ *   bad = the first i that breaks a rule of its own, or whose pair (i, i+1) breaks an order rule
+ *   if bad exists:
+ *       result = {0, 0, 0, bad + 1}; bin_first[0 .. nh+3] = 0
+ *       route, order, calls_out and replies are not written; return
+ *
+ *   for r in 0 .. n-1:
+ *       m = msgs[r]
+ *       if   status[r] != ONC_OK:          bin = nh + 2          # the descriptor is not looked at
+ *       elif m.msg_type != ONC_MSG_CALL:   bin = nh + 1
+ *       else:
+ *           e = the entry with program == m.program, version == m.program_version,
+ *               proc_first <= m.procedure < proc_first + proc_count            # at most one
+ *           if e:                      bin = handler of m.procedure by e; stat = ONC_ACCEPT_SUCCESS
+ *           elif any entry has (m.program, m.program_version):
+ *                                      bin = nh; stat = ONC_ACCEPT_PROC_UNAVAIL
+ *           elif any entry has m.program:
+ *                                      bin = nh; stat = ONC_ACCEPT_PROG_MISMATCH
+ *                                      low / high = least / greatest version among that program's entries
+ *           else:                      bin = nh; stat = ONC_ACCEPT_PROG_UNAVAIL
+ *       route[r] = bin
+ *
+ *   order = the record indices sorted by route[], stably (ascending r inside a bin)
+ *   bin_first[b] = number of records in bins < b, for b in 0 .. nh+3      # bin b is order[bin_first[b] .. bin_first[b+1])
+ *   for k in 0 .. n-1:
+ *       r = order[k]
+ *       if calls_out: calls_out[k] = msgs[r]          # all 64 bytes, untouched, in every bin
+ *       if replies:   replies[k] = all zero, unless r is an OK Call; then:
+ *           xid = msgs[r].xid; msg_type = ONC_MSG_REPLY; reply_stat = ONC_REPLY_ACCEPTED; stat = stat above
+ *           u.mismatch = {low, high, 0} for PROG_MISMATCH, else zero
+ *           verf = AuthNone(None): id 0, kind_len ONC_AUTH_PACK(ONC_KIND_NONE, 0), ref 0
+ *           cred zero; payload_len = payload_off = 0
+ *   result = {Calls in handler bins, Calls in the rejected bin, records in the last two bins, 0}
+ *
+ *  - replies + bin_first[nh], count bin_first[nh+1] - bin_first[nh], is an
+ *    onc_batch.msgs that onc_encode serialises as it stands, without arenas:
+ *    the finished error replies. A handler fills payload_off / payload_len of
+ *    its own slice replies[bin_first[h] .. bin_first[h+1]) and encodes that.
+ *    `order` carries whatever else the caller keeps per record (rec_seg, slot
+ *    offsets) into the same order.
+ *  - ntab == 0 is a valid table: every Call is PROG_UNAVAIL. nh == 0 is valid
+ *    too, and only an empty table satisfies it.
+ *  - The checks come before anything is launched, pointers before alignment.
+ *    ONC_RC_EINVAL: a NULL codec, result or bin_first; ntab >
+ *    ONC_ROUTE_TABLE_MAX; nh > ONC_ROUTE_HANDLERS_MAX; n >= 2^32 (an order
+ *    entry is 32 bits); ntab > 0 with a NULL table; with n > 0 a NULL msgs,
+ *    status, route or order; calls_out == msgs or replies == msgs (a
+ *    permutation cannot be done in place); calls_out == replies when both are
+ *    given. ONC_RC_EALIGN: msgs, calls_out or replies not 16-byte aligned,
+ *    bin_first or result not 8-byte aligned, table not 4-byte aligned.
+ *    n == 0 still validates the table and writes bin_first (zeros) and result.
+ * The call is asynchronous on the codec's stream and every step is a kernel
+ * launch (no memset or memcpy node: a captured call replays). Scratch: the
+ * per-tile bin counts and a total per bin, (tiles + 1) × (nh + 3) × 4 bytes
+ * with ONC_ROUTE_TILE records a tile (about a byte per record at 256 bins), in
+ * onc_defragment's buffer: onc_codec_reserve(max_records >= n) covers it;
+ * growing it inside a capture is ONC_RC_ECAPTURE. The classify and scan
+ * launches report under ONC_K_DEFRAG_PLAN and the scatter under
+ * ONC_K_DEFRAG_COPY.
+ * Kernels (route.hip), the launch boundary being the only barrier between
+ * workgroups: route_classify (a workgroup per tile: the table staged in LDS
+ * and validated by every workgroup, the first publishing result[3]; a lane
+ * per record loads its status and, for an OK record only, the descriptor's
+ * first two 16-byte granules, binary-searches the table, writes route[] and
+ * counts the tile's records per bin in LDS; the counts go to the scratch
+ * bin-major), route_scan_bins (a workgroup per bin: the bin's tile counts
+ * scanned in place, its total kept), route_scan_total (one workgroup: the
+ * totals scanned into bin_first, and result), route_scatter (a workgroup per
+ * tile: route[] re-read, every record ranked stably — inside a wave among the
+ * peers of its bin, found with one ballot per bin bit, across waves by
+ * per-wave counts added in wave order — then order[], calls_out and replies
+ * as whole 16-byte stores; a rejected Call's stat, low and high are derived
+ * again from the table in LDS, nothing is carried in route[] or beside it).
+ * All keys are compared unsigned, proc_first + proc_count is formed in 64
+ * bits, and every index that addresses memory is 64-bit. */
+int onc_route_calls(onc_codec* codec, const onc_msg* msgs, const int32_t* status, uint64_t n,
+                    const onc_route* table /*[dev, ntab]*/, uint32_t ntab, uint32_t nh,
+                    uint32_t* route     /*[dev, n]*/,
+                    uint32_t* order     /*[dev, n]*/,
+                    uint64_t* bin_first /*[dev, nh + 4]*/,
+                    onc_msg*  calls_out /*[dev, n], optional*/,
+                    onc_msg*  replies   /*[dev, n], optional*/,
+                    uint64_t* result    /*[dev, 4]*/);
 
 /* Exclusive scan of record lengths into offsets:
  * rec_off[0] = base, rec_off[i+1] = rec_off[i] + rec_len[i]  ([dev]). */

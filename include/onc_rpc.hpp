@@ -60,6 +60,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <variant>
 #include <vector>
@@ -2050,6 +2051,163 @@ inline PlacedPayloads place_payloads(Codec& codec, const uint8_t* wire, size_t w
     }
     const detail::PlaceSource s{wire, wire_len, start.data(), len.data(), n, nullptr, nullptr, len.data(), start.data(), 0};
     return detail::place_decoded(codec, s, msgs.data(), status.data(), n, align);
+}
+
+// ----------------------------------------------------------------------------
+// Dispatch: decoded Calls to their handlers (onc_route_calls)
+// ----------------------------------------------------------------------------
+// A server's route table: which handler serves procedures [proc_first,
+// proc_first + proc_count) of a (program, version). Rows are given in any
+// order; sorted() puts them in the order the device wants and refuses
+// overlapping ranges, empty ranges, unknown flags and handlers beyond
+// n_handlers() on the host (CodecError), so the device never sees a bad table.
+class RouteTable {
+public:
+    explicit RouteTable(uint32_t n_handlers) : nh_(n_handlers) {
+        if (n_handlers > ONC_ROUTE_HANDLERS_MAX) throw CodecError("RouteTable: too many handlers");
+    }
+    // handler of procedure p: handler_first + (p - proc_first), or
+    // handler_first for every p with ONC_ROUTE_ONE_HANDLER in flags
+    RouteTable& add(uint32_t program, uint32_t version, uint32_t proc_first, uint32_t proc_count,
+                    uint32_t handler_first, uint32_t flags = 0) {
+        if (rows_.size() == ONC_ROUTE_TABLE_MAX) throw CodecError("RouteTable: too many entries");
+        rows_.push_back(onc_route{program, version, proc_first, proc_count, handler_first, flags});
+        return *this;
+    }
+    uint32_t n_handlers() const { return nh_; }
+    size_t size() const { return rows_.size(); }
+    std::vector<onc_route> sorted() const {
+        std::vector<onc_route> t = rows_;
+        std::sort(t.begin(), t.end(), [](const onc_route& a, const onc_route& b) {
+            return std::tie(a.program, a.version, a.proc_first) < std::tie(b.program, b.version, b.proc_first);
+        });
+        for (size_t i = 0; i < t.size(); ++i) {
+            const onc_route& e = t[i];
+            const uint64_t end = uint64_t(e.proc_first) + e.proc_count;
+            if (e.proc_count == 0 || end > (uint64_t(1) << 32)) throw CodecError("RouteTable: an empty or wrapping range");
+            if (e.flags & ~uint32_t(ONC_ROUTE_ONE_HANDLER)) throw CodecError("RouteTable: unknown flags");
+            if (uint64_t(e.handler_first) + ((e.flags & ONC_ROUTE_ONE_HANDLER) ? 1u : e.proc_count) > nh_)
+                throw CodecError("RouteTable: a handler beyond n_handlers");
+            if (i + 1 < t.size() && t[i + 1].program == e.program && t[i + 1].version == e.version &&
+                t[i + 1].proc_first < end)
+                throw CodecError("RouteTable: procedure ranges overlap");
+        }
+        return t;
+    }
+
+private:
+    uint32_t nh_;
+    std::vector<onc_route> rows_;
+};
+
+// What route_calls returns: the records grouped stably by bin — handler h's
+// Calls, the Calls no route serves, the records that are no Calls, the failed
+// ones — as positions in `order`. calls[k] / replies[k] describe record
+// order[k]: its Call descriptor (xid, program, version, procedure; the
+// payload and the auths stay in the Decoded result order[k] points at) and its
+// reply descriptor (a Success skeleton for a served Call, the finished RFC 5531
+// §9 rejection for the others).
+struct RoutedCalls {
+    struct Span {
+        const onc_msg* calls = nullptr;    // n Call descriptors, in arrival order
+        const onc_msg* replies = nullptr;  // their reply descriptors
+        const uint32_t* index = nullptr;   // their positions in the decoded batch
+        size_t n = 0;
+    };
+    uint32_t nh = 0;
+    std::vector<uint32_t> order;           // n
+    std::vector<uint64_t> bin_first;       // nh + 4
+    std::vector<onc_msg> calls, replies;   // n each
+    size_t n_served = 0, n_rejected = 0, n_other = 0;
+
+    Span bin(uint32_t b) const {
+        const size_t lo = size_t(bin_first[b]);
+        return Span{calls.data() + lo, replies.data() + lo, order.data() + lo, size_t(bin_first[b + 1]) - lo};
+    }
+    Span handler(uint32_t h) const {
+        if (h >= nh) throw CodecError("RoutedCalls: no such handler");
+        return bin(h);
+    }
+    Span rejected() const { return bin(ONC_ROUTE_BIN_REJECTED(nh)); }
+    Span not_calls() const { return bin(ONC_ROUTE_BIN_NOT_CALL(nh)); }
+    Span failed() const { return bin(ONC_ROUTE_BIN_FAILED(nh)); }
+
+    // The rejected Calls' replies (PROG_UNAVAIL, PROG_MISMATCH{low, high},
+    // PROC_UNAVAIL with an AUTH_NONE verifier), serialised back to back and
+    // appended to `out` through BatchEncoder; rec_off as serialise_into's.
+    std::vector<int32_t> reject_replies(Codec& codec, std::vector<uint8_t>& out,
+                                        std::vector<uint64_t>* rec_off = nullptr) const {
+        const Span r = rejected();
+        BatchEncoder enc;
+        for (size_t k = 0; k < r.n; ++k) {
+            const onc_msg& d = r.replies[k];
+            AcceptedStatus s = d.stat == ONC_ACCEPT_PROG_MISMATCH
+                                   ? AcceptedStatus::program_mismatch(d.u.mismatch.low, d.u.mismatch.high)
+                                   : AcceptedStatus::of(d.stat == ONC_ACCEPT_PROG_UNAVAIL
+                                                            ? AcceptedStatus::Kind::ProgramUnavailable
+                                                            : AcceptedStatus::Kind::ProcedureUnavailable);
+            enc.push(RpcMessage(d.xid, MessageType::reply(ReplyBody::accepted(AcceptedReply(AuthFlavor::none(), std::move(s))))));
+        }
+        if (!r.n) {
+            if (rec_off) rec_off->assign(1, 0);
+            return {};
+        }
+        return enc.serialise_into(codec, out, rec_off);
+    }
+};
+
+// onc_route_calls over a BatchDecoder result: every record classified against
+// the table on the device and grouped by handler. Inputs and outputs go through
+// the codec's stage; one synchronisation.
+inline RoutedCalls route_calls(Codec& codec, const std::vector<Decoded>& results, const RouteTable& table) {
+    using detail::need;
+    const std::vector<onc_route> t = table.sorted();
+    const size_t n = results.size(), ntab = t.size();
+    const uint32_t nh = table.n_handlers();
+    if (n >= (uint64_t(1) << 32)) throw CodecError("route_calls: too many records");
+    detail::Carve c{codec.stage(3 * need<onc_msg>(n) + need<int32_t>(n) + need<onc_route>(ntab) + 2 * need<uint32_t>(n) +
+                                need<uint64_t>(nh + 4) + need<uint64_t>(4))};
+    const auto dm = c.take<onc_msg>(n);
+    const auto st = c.take<int32_t>(n);
+    const auto tb = c.take<onc_route>(ntab);
+    const auto route = c.take<uint32_t>(n);
+    const auto order = c.take<uint32_t>(n);
+    const auto first = c.take<uint64_t>(nh + 4);
+    const auto co = c.take<onc_msg>(n);
+    const auto rp = c.take<onc_msg>(n);
+    const auto res = c.take<uint64_t>(4);
+    for (size_t r = 0; r < n; ++r) {
+        onc_msg& d = dm.host[r];
+        std::memset(&d, 0, sizeof(d));
+        st.host[r] = results[r].status;
+        if (!results[r].ok()) continue;
+        const RpcMessage& m = *results[r].message;
+        d.xid = m.xid();
+        if (const CallBody* cb = m.call_body()) {
+            d.msg_type = ONC_MSG_CALL;
+            d.u.call.program = cb->program();
+            d.u.call.program_version = cb->program_version();
+            d.u.call.procedure = cb->procedure();
+        } else {
+            d.msg_type = ONC_MSG_REPLY;
+        }
+    }
+    if (ntab) std::memcpy(tb.host, t.data(), sizeof(onc_route) * ntab);
+    codec.check(onc_route_calls(codec.get(), dm.dev, st.dev, n, ntab ? tb.dev : nullptr, uint32_t(ntab), nh, route.dev,
+                                order.dev, first.dev, co.dev, rp.dev, res.dev),
+                "onc_route_calls");
+    codec.sync();
+    if (res.host[3] != 0) throw CodecError("route_calls: the device refused the table");
+    RoutedCalls out;
+    out.nh = nh;
+    out.order.assign(order.host, order.host + n);
+    out.bin_first.assign(first.host, first.host + nh + 4);
+    out.calls.assign(co.host, co.host + n);
+    out.replies.assign(rp.host, rp.host + n);
+    out.n_served = size_t(res.host[0]);
+    out.n_rejected = size_t(res.host[1]);
+    out.n_other = size_t(res.host[2]);
+    return out;
 }
 
 inline FragmentedHeads BatchDecoder::try_from_fragmented_heads(Codec& codec, const uint8_t* wire, size_t wire_len,

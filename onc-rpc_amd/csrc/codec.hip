@@ -1709,6 +1709,55 @@ int onc_place_payloads(onc_codec* c, const uint8_t* wire, const uint64_t* frag_s
     return run(c, ONC_K_DEFRAG_COPY, "place_copy", [&] { return onc::launch_place_copy(a, c->stream); });
 }
 
+int onc_route_calls(onc_codec* c, const onc_msg* msgs, const int32_t* status, uint64_t n, const onc_route* table,
+                    uint32_t ntab, uint32_t nh, uint32_t* route, uint32_t* order, uint64_t* bin_first,
+                    onc_msg* calls_out, onc_msg* replies, uint64_t* result) {
+    if (!c || !result || !bin_first) return ONC_RC_EINVAL;
+    if (ntab > ONC_ROUTE_TABLE_MAX || nh > ONC_ROUTE_HANDLERS_MAX || n >= (1ull << 32)) return ONC_RC_EINVAL;
+    if (ntab && !table) return ONC_RC_EINVAL;
+    if (n && (!msgs || !status || !route || !order)) return ONC_RC_EINVAL;
+    // a permutation cannot be done in place
+    if (msgs && (calls_out == msgs || replies == msgs)) return ONC_RC_EINVAL;
+    if (calls_out && calls_out == replies) return ONC_RC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(msgs) & 15) || (reinterpret_cast<uintptr_t>(calls_out) & 15) ||
+        (reinterpret_cast<uintptr_t>(replies) & 15) || (reinterpret_cast<uintptr_t>(bin_first) & 7) ||
+        (reinterpret_cast<uintptr_t>(result) & 7) || (reinterpret_cast<uintptr_t>(table) & 3))
+        return ONC_RC_EALIGN;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    onc::RouteArgs a{};
+    a.msgs = msgs;
+    a.status = status;
+    a.n = n;
+    a.table = table;
+    a.ntab = ntab;
+    a.nh = nh;
+    a.route = route;
+    a.order = order;
+    a.bin_first = bin_first;
+    a.calls_out = calls_out;
+    a.replies = replies;
+    a.result = result;
+    a.tiles = onc::route_tiles(n, onc::kRouteTile);
+    // onc_defragment's buffer, a record where it keeps a fragment: the bin
+    // counts, 4 (nh + 3) (n / 1024 + 2) <= 1.02 n + 2072 bytes of its 28 per
+    // fragment (for at least 65536 of them: ensure_defrag's floor). No records
+    // still scan the bins' totals: the buffer is there for them too.
+    int rc = ensure_defrag(c, n ? n : 1);
+    if (rc != ONC_RC_OK) return rc;
+    static_assert(4ull * (ONC_ROUTE_HANDLERS_MAX + 3) * (65536 / onc::kRouteTile + 2) <= 28ull * 65536,
+                  "the counts of a batch below the floor fit the floor");
+    a.counts = reinterpret_cast<uint32_t*>(c->dfr);
+    a.totals = a.counts + uint64_t(onc::route_bins(nh)) * a.tiles;
+    rc = run(c, ONC_K_DEFRAG_PLAN, "route_classify", [&] { return onc::launch_route_classify(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "route_scan_bins", [&] { return onc::launch_route_scan_bins(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "route_scan_total", [&] { return onc::launch_route_scan_total(a, c->stream); });
+    if (rc == ONC_RC_OK && n)
+        rc = run(c, ONC_K_DEFRAG_COPY, "route_scatter", [&] { return onc::launch_route_scatter(a, c->stream); });
+    return rc;
+}
+
 int32_t onc_expected_message_len(const uint8_t* data, uint64_t len, uint32_t* out) {
     if (out) *out = 0;
     if (!data || len < 4) return ONC_ERR_INCOMPLETE_HEADER;          // rpc_message.rs:344-346

@@ -14,6 +14,7 @@
 #include "fragment_plan.h"
 #include "gather_plan.h"
 #include "payload_plan.h"
+#include "route_plan.h"
 
 namespace onc {
 
@@ -274,6 +275,26 @@ struct PlaceArgs {
     uint64_t dst_cap;           // the caller's capacity
 };
 
+// onc_route_calls (route.hip). Scratch: the tiles' bin counts, bin-major, and
+// a total per bin (4 bytes each), in onc_defragment's buffer.
+struct RouteArgs {
+    const onc_msg* msgs;        // n, 16-byte aligned
+    const int32_t* status;      // n
+    uint64_t n;                 // < 2^32
+    const onc_route* table;     // ntab, 4-byte aligned
+    uint32_t ntab;              // <= ONC_ROUTE_TABLE_MAX
+    uint32_t nh;                // <= ONC_ROUTE_HANDLERS_MAX
+    uint32_t* route;            // n
+    uint32_t* order;            // n
+    uint64_t* bin_first;        // nh + 4
+    onc_msg* calls_out;         // n, optional
+    onc_msg* replies;           // n, optional
+    uint64_t* result;           // [4]
+    uint64_t tiles;             // route_tiles(n, kRouteTile)
+    uint32_t* counts;           // (nh + 3) * tiles (route_count_at)
+    uint32_t* totals;           // nh + 3
+};
+
 struct DecArgs {
     uint64_t n;
     const uint8_t* wire;
@@ -437,6 +458,11 @@ hipError_t launch_pay_blkscan(const PaySlotsArgs& a, hipStream_t s);
 hipError_t launch_pay_apply(const PaySlotsArgs& a, hipStream_t s);
 hipError_t launch_pay_empty(const PaySlotsArgs& a, hipStream_t s);
 hipError_t launch_place_copy(const PlaceArgs& a, hipStream_t s);
+// route.hip
+hipError_t launch_route_classify(const RouteArgs& a, hipStream_t s);
+hipError_t launch_route_scan_bins(const RouteArgs& a, hipStream_t s);
+hipError_t launch_route_scan_total(const RouteArgs& a, hipStream_t s);
+hipError_t launch_route_scatter(const RouteArgs& a, hipStream_t s);
 // streams.hip
 hipError_t launch_streams_chase(const StreamsArgs& a, hipStream_t s);
 hipError_t launch_streams_write(const StreamsArgs& a, hipStream_t s);

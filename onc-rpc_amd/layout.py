@@ -93,6 +93,14 @@ FRAG_PIECE_DTYPE = np.dtype({
     "itemsize": 16,
 })
 PIECE_MARK, PIECE_HDR, PIECE_PAYLOAD = 0, 1, 2
+# onc_route (onc_route_calls): procedures [proc_first, proc_first + proc_count)
+# of one (program, version) and their handlers
+ROUTE_DTYPE = np.dtype({
+    "names": ["program", "version", "proc_first", "proc_count", "handler_first", "flags"],
+    "formats": ["<u4"] * 6,
+    "offsets": [0, 4, 8, 12, 16, 20],
+    "itemsize": 24,
+})
 
 
 def pack_kind_len(kind, length):

@@ -47,6 +47,7 @@ EXPORTED = [
     "onc_defragment_heads", "onc_decode_heads",
     "onc_piece_offsets", "onc_gather_pieces",
     "onc_payload_slots", "onc_place_payloads",
+    "onc_route_calls",
 ]
 
 # onc_codec_options (include/onc_rpc.h)
@@ -145,6 +146,7 @@ def load_library(path=LIB_PATH):
     lib.onc_gather_pieces.argtypes = [vp, vp, vp, u64, C.POINTER(OncGatherSrc), u64, u64, vp]
     lib.onc_payload_slots.argtypes = [vp, vp, vp, u64, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, vp]
     lib.onc_place_payloads.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp, u64]
+    lib.onc_route_calls.argtypes = [vp, vp, vp, u64, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
     for name in EXPORTED:
         getattr(lib, name).restype = getattr(lib, name).restype or i32
     # a stale library would read a differently laid out onc_batch and label
@@ -403,6 +405,18 @@ class Codec:
         self._check(self.lib.onc_place_payloads(self.h, _ptr(wire), _ptr(frag_start), _ptr(frag_len), nfrag,
                                                 _ptr(rec_frag), _ptr(frag_pre), _ptr(rec_len), _ptr(pay_pos),
                                                 _ptr(pay_len), _ptr(slot_off), n, dptr, cap), "onc_place_payloads")
+
+    def route_calls(self, msgs, status, n, table, ntab, nh, route, order, bin_first, result, calls_out=None,
+                    replies=None):
+        """onc_route_calls: every decoded record classified against the route
+        table (L.ROUTE_DTYPE rows, sorted) into one of nh + 3 bins (route[n]),
+        the records grouped stably by bin (order[n], bin_first[nh + 4]), and
+        optionally the descriptors (calls_out) and the reply descriptors
+        (replies) in that order; result = {Calls served, Calls rejected, other
+        records, first bad table entry + 1}."""
+        self._check(self.lib.onc_route_calls(self.h, _ptr(msgs), _ptr(status), n, _ptr(table), ntab, nh, _ptr(route),
+                                             _ptr(order), _ptr(bin_first), _ptr(calls_out), _ptr(replies),
+                                             _ptr(result)), "onc_route_calls")
 
     def frame_streams(self, wire, seg_off, seg_len, nseg, rec_start, rec_len, rec_seg, max_records, seg_result,
                       result):
@@ -917,6 +931,52 @@ def payload_slots_host(codec: Codec, msgs, status, align, head_len=0, rec_start=
     return {"pay_pos": raw["pay_pos"][:n], "pay_len": raw["pay_len"][:n], "slot_off": raw["slot_off"][:n + 1],
             "result": raw["result"][:3],
             "msgs_out": None if d_out is None else raw["msgs_out"][:n * 64].view(L.MSG_DTYPE), "raw": raw}
+
+
+ROUTE_TILE = 1024           # ONC_ROUTE_TILE: records per workgroup of onc_route_calls' kernels
+ROUTE_TABLE_MAX, ROUTE_HANDLERS_MAX, ROUTE_ONE_HANDLER = 1024, 253, 1
+
+
+def route_table(rows):
+    """(program, version, proc_first, proc_count, handler_first, flags) rows ->
+    an L.ROUTE_DTYPE array, as given (onc_route_calls wants them sorted)."""
+    t = np.zeros(len(rows), L.ROUTE_DTYPE)
+    for i, row in enumerate(rows):
+        t[i] = tuple(row)
+    return t
+
+
+def route_calls_host(codec: Codec, msgs, status, table, nh, calls_out=True, replies=True, extra=4, device="cuda"):
+    """Convenience: host descriptors (L.MSG_DTYPE), statuses and a route table
+    (L.ROUTE_DTYPE) -> onc_route_calls -> a dict of host arrays: route[n],
+    order[n], bin_first[nh + 4], result[4], calls_out[n] and replies[n] (None
+    when not asked for), and `raw`: the whole output arrays with `extra` words
+    behind them, pre-filled with sentinels (-1; descriptors 0xA5), so that a
+    caller can see what was left alone."""
+    torch = _torch()
+    m = np.ascontiguousarray(msgs, L.MSG_DTYPE)
+    t = np.ascontiguousarray(table, L.ROUTE_DTYPE)
+    n = len(m)
+    d_msgs = to_device(m, device)
+    d_st = _dev_words(status, np.int32, np.int32, device)
+    d_tab = to_device(t, device) if len(t) else None
+    route = torch.full((n + extra,), -1, dtype=torch.int32, device=device)
+    order = torch.full((n + extra,), -1, dtype=torch.int32, device=device)
+    bin_first = torch.full((nh + 4 + extra,), -1, dtype=torch.int64, device=device)
+    res = torch.full((4 + extra,), -1, dtype=torch.int64, device=device)
+    d_calls = torch.full(((n + extra) * 64,), 0xA5, dtype=torch.uint8, device=device) if calls_out else None
+    d_rep = torch.full(((n + extra) * 64,), 0xA5, dtype=torch.uint8, device=device) if replies else None
+    codec.route_calls(d_msgs, d_st, n, d_tab, len(t), nh, route, order, bin_first, res, calls_out=d_calls,
+                      replies=d_rep)
+    codec.sync()
+    raw = {"route": route.cpu().numpy().view(np.uint32).copy(), "order": order.cpu().numpy().view(np.uint32).copy(),
+           "bin_first": bin_first.cpu().numpy().view(np.uint64).copy(), "result": res.cpu().numpy().view(np.uint64).copy(),
+           "calls_out": None if d_calls is None else d_calls.cpu().numpy().copy(),
+           "replies": None if d_rep is None else d_rep.cpu().numpy().copy()}
+    return {"route": raw["route"][:n], "order": raw["order"][:n], "bin_first": raw["bin_first"][:nh + 4],
+            "result": raw["result"][:4],
+            "calls_out": None if d_calls is None else raw["calls_out"][:n * 64].view(L.MSG_DTYPE),
+            "replies": None if d_rep is None else raw["replies"][:n * 64].view(L.MSG_DTYPE), "raw": raw}
 
 
 def place_payloads_host(codec: Codec, wire, frag_start, frag_len, rec_frag, frag_pre, rec_len, pay_pos, pay_len,

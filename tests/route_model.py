@@ -1,0 +1,124 @@
+"""onc_route_calls restated in numpy / plain Python from the pseudocode of
+include/onc_rpc.h: the expected value of every route test. The lookup is a
+linear scan over the entries, not a binary search, so that it does not share
+the kernels' bug class. Pure host logic."""
+import numpy as np
+
+import onc_rpc_amd.layout as L
+
+ACCEPT_SUCCESS, PROG_UNAVAIL, PROG_MISMATCH, PROC_UNAVAIL = 0, 1, 2, 3
+ONE_HANDLER = 1
+TABLE_MAX, HANDLERS_MAX = 1024, 253
+
+
+def table(rows):
+    """(program, version, proc_first, proc_count, handler_first, flags) rows, as given."""
+    t = np.zeros(len(rows), L.ROUTE_DTYPE)
+    for i, row in enumerate(rows):
+        t[i] = tuple(row)
+    return t
+
+
+def _entry_ok(e, nh):
+    pf, pc, hf, fl = int(e["proc_first"]), int(e["proc_count"]), int(e["handler_first"]), int(e["flags"])
+    if pc < 1 or pf + pc > 1 << 32 or fl & ~1:
+        return False
+    return hf + (1 if fl & ONE_HANDLER else pc) <= nh
+
+
+def _pair_ok(a, b):
+    ka = (int(a["program"]), int(a["version"]), int(a["proc_first"]))
+    kb = (int(b["program"]), int(b["version"]), int(b["proc_first"]))
+    if not ka < kb:
+        return False
+    if ka[:2] == kb[:2]:
+        return int(a["proc_first"]) + int(a["proc_count"]) <= int(b["proc_first"])
+    return True
+
+
+def first_bad(tab, nh):
+    """The first entry that breaks a rule of its own or whose pair (i, i + 1)
+    breaks an order rule, + 1; 0 for a valid table."""
+    for i in range(len(tab)):
+        if not _entry_ok(tab[i], nh):
+            return i + 1
+        if i + 1 < len(tab) and not _pair_ok(tab[i], tab[i + 1]):
+            return i + 1
+    return 0
+
+
+def _rows(tab):
+    return [tuple(int(x) for x in e) for e in tab]
+
+
+def lookup(tab, nh, program, version, proc):
+    """A Call's (bin, stat, low, high) in a valid table."""
+    return _lookup(_rows(tab), nh, program, version, proc)
+
+
+def _lookup(rows, nh, program, version, proc):
+    same_pv, versions = False, []
+    for p, v, pf, pc, hf, fl in rows:
+        if p != program:
+            continue
+        versions.append(v)
+        if v != version:
+            continue
+        same_pv = True
+        if pf <= proc < pf + pc:
+            return hf + (0 if fl & ONE_HANDLER else proc - pf), ACCEPT_SUCCESS, 0, 0
+    if same_pv:
+        return nh, PROC_UNAVAIL, 0, 0
+    if versions:
+        return nh, PROG_MISMATCH, min(versions), max(versions)
+    return nh, PROG_UNAVAIL, 0, 0
+
+
+def route_calls(msgs, status, tab, nh):
+    """-> dict(result[4], bin_first[nh + 4], route[n], order[n], calls_out[n],
+    replies[n], stat[n]); with a bad table only result and bin_first (the
+    other arrays are None: they are not written)."""
+    msgs = np.ascontiguousarray(msgs, L.MSG_DTYPE)
+    status = np.asarray(status, np.int32)
+    n = len(msgs)
+    assert len(tab) <= TABLE_MAX and nh <= HANDLERS_MAX and n < 1 << 32
+    bad = first_bad(tab, nh)
+    if bad:
+        return {"result": np.array([0, 0, 0, bad], np.uint64), "bin_first": np.zeros(nh + 4, np.uint64),
+                "route": None, "order": None, "calls_out": None, "replies": None, "stat": None}
+    rows, seen = _rows(tab), {}
+    route = np.zeros(n, np.uint32)
+    replies = np.zeros(n, L.MSG_DTYPE)
+    stat = np.zeros(n, np.uint32)
+    for r in range(n):
+        m = msgs[r]
+        if status[r] != 0:
+            route[r] = nh + 2
+        elif int(m["msg_type"]) != L.MSG_CALL:
+            route[r] = nh + 1
+        else:
+            key = (int(m["f0"]), int(m["f1"]), int(m["f2"]))
+            if key not in seen:                      # (the same linear scan, once per distinct key)
+                seen[key] = _lookup(rows, nh, *key)
+            b, st, low, high = seen[key]
+            route[r], stat[r] = b, st
+            rep = replies[r]
+            rep["xid"], rep["msg_type"], rep["reply_stat"], rep["stat"] = m["xid"], L.MSG_REPLY, L.REPLY_ACCEPTED, st
+            rep["f0"], rep["f1"] = low, high
+            rep["verf_kind_len"] = L.pack_kind_len(L.KIND_NONE, 0)
+    order = np.argsort(route, kind="stable").astype(np.uint32)
+    counts = np.bincount(route, minlength=nh + 3).astype(np.uint64)
+    bin_first = np.zeros(nh + 4, np.uint64)
+    np.cumsum(counts, out=bin_first[1:])
+    result = np.array([bin_first[nh], counts[nh], counts[nh + 1] + counts[nh + 2], 0], np.uint64)
+    return {"result": result, "bin_first": bin_first, "route": route, "order": order, "calls_out": msgs[order],
+            "replies": replies[order], "stat": stat}
+
+
+def calls(keys, xid0=1):
+    """(program, version, procedure) triples -> OK Call descriptors with AUTH_NONE auths."""
+    m = np.zeros(len(keys), L.MSG_DTYPE)
+    for i, (p, v, c) in enumerate(keys):
+        m[i]["xid"], m[i]["msg_type"] = (xid0 + i) & 0xFFFFFFFF, L.MSG_CALL
+        m[i]["f0"], m[i]["f1"], m[i]["f2"] = p, v, c
+    return m
