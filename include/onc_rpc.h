@@ -94,7 +94,9 @@ extern "C" {
  *    aligned slots on the device), which add no status code and reuse
  *    onc_defragment's timing ids; onc_route_calls with onc_route (decoded
  *    Calls dispatched to handlers on the device), which adds no status code
- *    and reuses onc_defragment's timing ids. */
+ *    and reuses onc_defragment's timing ids; onc_match_replies with
+ *    onc_pending (decoded Replies paired with pending Calls on the device),
+ *    which adds no status code and reuses onc_defragment's timing ids. */
 #define ONC_RPC_ABI_VERSION 8
 
 /* ------------------------------------------------------------------------ */
@@ -416,6 +418,7 @@ typedef struct onc_codec onc_codec;
 #define ONC_VARIANT_WS_PIPELINE      0x10000u  /* wave-specialised: the pipeline on header-heavy batches too */
 #define ONC_VARIANT_EMIT_REPLAN      0x20000u  /* wave-per-tile enc_emit re-plans instead of reading the plan's lengths */
 #define ONC_VARIANT_WHOLE_PLAN       0x40000u  /* plan a large batch whole instead of in chunks */
+#define ONC_VARIANT_MATCH_ONE_CHAIN  0x80000u  /* onc_match_replies: every key hashes to slot S - 2 (one wrapping chain) */
 
 #define ONC_OPT_FORCE_SCAN 0x1u   /* always launch the separate block-scan kernels (tests of that path) */
 
@@ -461,7 +464,11 @@ int onc_codec_sync(onc_codec* codec);
  * max_records records keeps its bin counts there as well (about 1 byte per
  * record at 256 bins, and 2 KiB of them however few the records): that buffer
  * is never smaller than 65536 fragments' worth (1.8 MB), so a reserve for a
- * handful of records covers the call at any table and handler count. */
+ * handful of records covers the call at any table and handler count.
+ * onc_match_replies of up to max_records records against up to max_records
+ * pending entries builds its slot table, first_rec and tile counts there too
+ * (under 32 bytes per pending entry plus under 1 byte per 32 records): a
+ * reserve of max(n, np) covers the call. */
 int onc_codec_reserve(onc_codec* codec, uint64_t max_records);
 /* Map a caller's host buffer (a socket buffer: any malloc'd or mmap'd
  * range) for the kernels, so that an encode / decode reads and writes it in
@@ -535,7 +542,11 @@ int onc_abi_version(void);
  * ONC_K_DEFRAG_PLAN and onc_place_payloads its copy (place_copy) under
  * ONC_K_DEFRAG_COPY. onc_route_calls reports its classify and scan launches
  * (route_classify, route_scan_bins, route_scan_total) under
- * ONC_K_DEFRAG_PLAN and its scatter (route_scatter) under ONC_K_DEFRAG_COPY. */
+ * ONC_K_DEFRAG_PLAN and its scatter (route_scatter) under ONC_K_DEFRAG_COPY.
+ * onc_match_replies reports its clear, insert, probe, resolve and scan
+ * launches (match_clear, match_insert, match_probe, match_resolve,
+ * match_scan) under ONC_K_DEFRAG_PLAN and its compaction (match_compact)
+ * under ONC_K_DEFRAG_COPY. */
 #define ONC_K_ENC_LEN      0
 #define ONC_K_SCAN_TILES   1
 #define ONC_K_ENC_EMIT     2
@@ -1411,7 +1422,7 @@ int onc_place_payloads(onc_codec* codec, const uint8_t* wire,
  * descriptors — complete for the Calls nobody serves, skeletons for the rest —
  * in an order onc_encode takes directly. Credential checks (AUTH_ERROR
  * rejections) and the matching of a client's Replies to its outstanding xids
- * are not part of it.
+ * are not part of it (the latter is onc_match_replies, below).
  *
  * A route: the procedures [proc_first, proc_first + proc_count) of one
  * (program, version). Procedure p goes to handler handler_first + (p -
@@ -1527,6 +1538,107 @@ int onc_route_calls(onc_codec* codec, const onc_msg* msgs, const int32_t* status
                     onc_msg*  calls_out /*[dev, n], optional*/,
                     onc_msg*  replies   /*[dev, n], optional*/,
                     uint64_t* result    /*[dev, 4]*/);
+
+/* The other half of every exchange: a client that sent Calls over many
+ * connections gets their Replies back in whatever order the servers finished
+ * them, and pairs each with the Call it answers by (connection, xid) (the
+ * reference leaves that loop to the application too: RpcMessage::xid() and
+ * reply_body(), nothing more). onc_match_replies is that loop as one batch
+ * call on the device: a hash join of the decoded records against the caller's
+ * list of pending Calls. The call keeps nothing between batches: the caller
+ * owns the pending list, the codec only scratch. */
+typedef struct onc_pending {      /* 16 bytes */
+    uint32_t conn;                /* the connection the Call went out on: what onc_frame_streams' rec_seg
+                                     says for its Reply. Any value, 0xFFFFFFFF included */
+    uint32_t xid;                 /* any value */
+    uint64_t tag;                 /* the caller's (a request slot, a send time): copied, never looked at */
+} onc_pending;
+
+#define ONC_MATCH_UNKNOWN   0xFFFFFFFFu  /* match[r]: an OK Reply whose (conn, xid) is not pending */
+#define ONC_MATCH_DUPLICATE 0xFFFFFFFEu  /* an OK Reply whose entry an earlier record of this batch answers */
+#define ONC_MATCH_NOT_REPLY 0xFFFFFFFDu  /* an OK record whose msg_type != ONC_MSG_REPLY */
+#define ONC_MATCH_FAILED    0xFFFFFFFCu  /* status != ONC_OK: neither descriptor nor rec_conn is looked at */
+#define ONC_MATCH_NONE      0xFFFFFFFFu  /* hit[p]: no record of this batch answers entry p */
+#define ONC_MATCH_MAX       0xFFFFFFF0u  /* n and np must be below it */
+#define ONC_MATCH_TILE      1024u        /* records / entries per workgroup (tests: the sizes around it) */
+
+/* onc_match_replies. The result is exactly that of
+ *
+ *   lead(c, x) = the lowest p with pending[p].conn == c and pending[p].xid == x, or none
+ *   for r in 0 .. n-1:
+ *       if   status[r] != ONC_OK:                 match[r] = FAILED
+ *       elif msgs[r].msg_type != ONC_MSG_REPLY:   match[r] = NOT_REPLY
+ *       else:
+ *           p = lead(rec_conn ? rec_conn[r] : 0, msgs[r].xid)
+ *           if   p is none:                                        match[r] = UNKNOWN
+ *           elif an r' < r is an OK Reply with the same lead p:    match[r] = DUPLICATE
+ *           else:                                                  match[r] = p
+ *   for p in 0 .. np-1:  hit[p] = the r with match[r] == p, or ONC_MATCH_NONE
+ *   if tag_out: tag_out[r] = pending[match[r]].tag when match[r] < np, else 0
+ *   if still:   still[0 .. k) = the entries with hit[p] == NONE, in ascending p, all 16 bytes untouched
+ *   result = {matched, unknown, duplicate, not_reply, failed, k}      # the first five sum to n; k is counted with still NULL too
+ *
+ *  - Repeated pending keys. An entry that repeats an earlier entry's (conn,
+ *    xid) is never hit while the earlier one stands: it stays in `still` and
+ *    becomes the lead once the earlier one is answered. Repeated xids are
+ *    answered first sent, first matched, over successive batches.
+ *  - The next pending list. `still` followed by the Calls sent since is the
+ *    pending list of the next call.
+ *  - No key value is reserved: (0, 0) and (0xFFFFFFFF, 0xFFFFFFFF) are
+ *    ordinary keys.
+ *  - reply_stat, stat and everything else in the descriptor is not looked at:
+ *    a denied Reply answers its Call as well. Of a failed record neither the
+ *    descriptor nor rec_conn is looked at.
+ *  - The checks come before anything is launched, pointers before alignment.
+ *    ONC_RC_EINVAL: a NULL codec or result; n or np >= ONC_MATCH_MAX; with
+ *    n > 0 a NULL msgs, status or match; with np > 0 a NULL pending or hit;
+ *    still == pending. ONC_RC_EALIGN: msgs, pending or still not 16-byte
+ *    aligned; tag_out or result not 8-byte aligned; rec_conn, match, hit or
+ *    status not 4-byte aligned. n == 0 still writes hit (all NONE), still (a
+ *    copy of the list) and result; np == 0 sends every OK Reply to UNKNOWN.
+ * The call is asynchronous on the codec's stream and every step is a kernel
+ * launch (no memset or memcpy node: a captured call replays). Every caller
+ * array is read and written with plain loads and stores only, so any of them
+ * may be mapped host memory; all atomics go to the scratch. Scratch: the slot
+ * table (S 32-bit slots, S the least power of two >= 2 np and >= 16),
+ * first_rec[np] and the tiles' counts — under 32 bytes per pending entry plus
+ * under 1 byte per 32 records — in onc_defragment's buffer:
+ * onc_codec_reserve(max_records >= max(n, np)) covers it; growing it inside a
+ * capture is ONC_RC_ECAPTURE. The clear, insert, probe, resolve and scan
+ * launches report under ONC_K_DEFRAG_PLAN and the compaction under
+ * ONC_K_DEFRAG_COPY.
+ * Kernels (match.hip), the launch boundary being the only barrier between
+ * workgroups — none waits for another, nothing spins on memory, and every
+ * probe loop ends after S slots: match_clear (slots and first_rec filled with
+ * 0xFFFFFFFF, 16-byte stores), match_insert (a lane per pending entry: hash
+ * of (conn, xid), linear probing; atomicCAS(slot, EMPTY, p) claims an empty
+ * slot; the index q it returns otherwise names the slot's key, pending[q]:
+ * equal keys atomicMin(slot, p), different keys the next slot; the kernel
+ * decides only from what the atomics return, so each key ends in exactly one
+ * slot holding its lowest index: which slot depends on the race, no output
+ * does), match_probe (a lane per record: the status and, for an OK record
+ * only, the descriptor's first 16-byte granule and rec_conn[r]; the chain
+ * walked with plain loads to an equal key or an empty slot; match[r]
+ * provisional; atomicMin(&first_rec[p], r)), match_resolve (a lane per record:
+ * a provisional p whose first_rec[p] != r becomes DUPLICATE, tag_out, the
+ * tile's five classes counted; a lane per pending entry: hit[p] =
+ * first_rec[p], the tile's unanswered entries counted), match_scan (one
+ * workgroup: the unanswered counts scanned, the class counts summed, result),
+ * match_compact (only with still: a lane per pending entry ranked among its
+ * tile's unanswered entries with a ballot and per-wave counts; the whole
+ * 16-byte entry moved). Every index that addresses memory is 64-bit.
+ * ONC_VARIANT_MATCH_ONE_CHAIN hashes every key to slot S - 2: the whole list
+ * is then one chain that wraps round the end of the table (quadratic: tests
+ * only); results are bit-identical. */
+int onc_match_replies(onc_codec* codec, const onc_msg* msgs, const int32_t* status,
+                      const uint32_t* rec_conn /*[dev, n], optional: NULL = every record on connection 0*/,
+                      uint64_t n,
+                      const onc_pending* pending /*[dev, np]*/, uint64_t np,
+                      uint32_t* match       /*[dev, n]*/,
+                      uint32_t* hit         /*[dev, np]*/,
+                      uint64_t* tag_out     /*[dev, n], optional*/,
+                      onc_pending* still    /*[dev, np], optional*/,
+                      uint64_t* result      /*[dev, 6]*/);
 
 /* Exclusive scan of record lengths into offsets:
  * rec_off[0] = base, rec_off[i+1] = rec_off[i] + rec_len[i]  ([dev]). */

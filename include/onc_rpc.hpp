@@ -2210,6 +2210,101 @@ inline RoutedCalls route_calls(Codec& codec, const std::vector<Decoded>& results
     return out;
 }
 
+// ---------------------------------------------------------------------------
+// Replies paired with the Calls they answer (onc_match_replies)
+// ---------------------------------------------------------------------------
+// A client's Calls that wait for their Replies, in the order they were sent:
+// add() one per Call with the connection it went out on and a tag of the
+// caller's (a request slot, a send time). The same (conn, xid) may be pending
+// more than once: its Replies answer the entries first sent, first matched.
+class PendingCalls {
+public:
+    PendingCalls() = default;
+    explicit PendingCalls(std::vector<onc_pending> list) : list_(std::move(list)) {}
+    PendingCalls& add(uint32_t conn, uint32_t xid, uint64_t tag = 0) {
+        if (list_.size() + 1 >= ONC_MATCH_MAX) throw CodecError("PendingCalls: too many entries");
+        list_.push_back(onc_pending{conn, xid, tag});
+        return *this;
+    }
+    const std::vector<onc_pending>& list() const { return list_; }
+    size_t size() const { return list_.size(); }
+    bool empty() const { return list_.empty(); }
+
+private:
+    std::vector<onc_pending> list_;
+};
+
+// What match_replies returns. match[r]: the pending entry record r answers, or
+// ONC_MATCH_UNKNOWN / _DUPLICATE / _NOT_REPLY / _FAILED; tag[r]: that entry's
+// tag (0 for a record that answers none); hit[p]: the record that answers
+// entry p, or ONC_MATCH_NONE.
+struct MatchedReplies {
+    std::vector<uint32_t> match;           // n
+    std::vector<uint64_t> tag;             // n
+    std::vector<uint32_t> hit;             // np
+    size_t n_matched = 0, n_unknown = 0, n_duplicate = 0, n_not_reply = 0, n_failed = 0;
+
+    bool matched(size_t r) const { return match[r] < ONC_MATCH_FAILED; }
+    bool answered(size_t p) const { return hit[p] != ONC_MATCH_NONE; }
+    // The entries nobody answered, in list order: followed by the Calls sent
+    // since, the pending list of the next batch.
+    const PendingCalls& still() const { return still_; }
+
+private:
+    PendingCalls still_;
+    friend MatchedReplies match_replies(Codec&, const std::vector<Decoded>&, const std::vector<uint32_t>&,
+                                        const PendingCalls&);
+};
+
+// onc_match_replies over a BatchDecoder result: record r arrived on connection
+// conns[r] (what try_from_streams' segments say; an empty `conns`: every record
+// on connection 0). Inputs and outputs go through the codec's stage; one
+// synchronisation.
+inline MatchedReplies match_replies(Codec& codec, const std::vector<Decoded>& results,
+                                    const std::vector<uint32_t>& conns, const PendingCalls& pending) {
+    using detail::need;
+    const size_t n = results.size(), np = pending.size();
+    if (!conns.empty() && conns.size() != n) throw CodecError("match_replies: a connection per record");
+    if (n >= ONC_MATCH_MAX || np >= ONC_MATCH_MAX) throw CodecError("match_replies: too many records");
+    detail::Carve c{codec.stage(need<onc_msg>(n) + need<int32_t>(n) + 2 * need<uint32_t>(n) + 2 * need<onc_pending>(np) +
+                                need<uint32_t>(np) + need<uint64_t>(n) + need<uint64_t>(6))};
+    const auto dm = c.take<onc_msg>(n);
+    const auto st = c.take<int32_t>(n);
+    const auto rc = c.take<uint32_t>(n);
+    const auto pd = c.take<onc_pending>(np);
+    const auto sl = c.take<onc_pending>(np);
+    const auto mt = c.take<uint32_t>(n);
+    const auto ht = c.take<uint32_t>(np);
+    const auto tg = c.take<uint64_t>(n);
+    const auto res = c.take<uint64_t>(6);
+    for (size_t r = 0; r < n; ++r) {
+        onc_msg& d = dm.host[r];
+        std::memset(&d, 0, sizeof(d));
+        st.host[r] = results[r].status;
+        rc.host[r] = conns.empty() ? 0u : conns[r];
+        if (!results[r].ok()) continue;
+        const RpcMessage& m = *results[r].message;
+        d.xid = m.xid();
+        d.msg_type = m.call_body() ? ONC_MSG_CALL : ONC_MSG_REPLY;
+    }
+    if (np) std::memcpy(pd.host, pending.list().data(), sizeof(onc_pending) * np);
+    codec.check(onc_match_replies(codec.get(), dm.dev, st.dev, conns.empty() ? nullptr : rc.dev, n, pd.dev, np, mt.dev,
+                                  ht.dev, tg.dev, sl.dev, res.dev),
+                "onc_match_replies");
+    codec.sync();
+    MatchedReplies out;
+    out.match.assign(mt.host, mt.host + n);
+    out.tag.assign(tg.host, tg.host + n);
+    out.hit.assign(ht.host, ht.host + np);
+    out.n_matched = size_t(res.host[0]);
+    out.n_unknown = size_t(res.host[1]);
+    out.n_duplicate = size_t(res.host[2]);
+    out.n_not_reply = size_t(res.host[3]);
+    out.n_failed = size_t(res.host[4]);
+    out.still_ = PendingCalls(std::vector<onc_pending>(sl.host, sl.host + size_t(res.host[5])));
+    return out;
+}
+
 inline FragmentedHeads BatchDecoder::try_from_fragmented_heads(Codec& codec, const uint8_t* wire, size_t wire_len,
                                                                const std::vector<Segment>& segments, DecodeMode mode,
                                                                uint32_t head_len) {

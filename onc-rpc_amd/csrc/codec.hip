@@ -1758,6 +1758,64 @@ int onc_route_calls(onc_codec* c, const onc_msg* msgs, const int32_t* status, ui
     return rc;
 }
 
+int onc_match_replies(onc_codec* c, const onc_msg* msgs, const int32_t* status, const uint32_t* rec_conn, uint64_t n,
+                      const onc_pending* pending, uint64_t np, uint32_t* match, uint32_t* hit, uint64_t* tag_out,
+                      onc_pending* still, uint64_t* result) {
+    if (!c || !result) return ONC_RC_EINVAL;
+    if (n >= ONC_MATCH_MAX || np >= ONC_MATCH_MAX) return ONC_RC_EINVAL;
+    if (n && (!msgs || !status || !match)) return ONC_RC_EINVAL;
+    if (np && (!pending || !hit)) return ONC_RC_EINVAL;
+    // a compaction cannot be done in place
+    if (still && still == pending) return ONC_RC_EINVAL;
+    const auto low = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (low(msgs, 15) || low(pending, 15) || low(still, 15) || low(tag_out, 7) || low(result, 7) || low(rec_conn, 3) ||
+        low(match, 3) || low(hit, 3) || low(status, 3))
+        return ONC_RC_EALIGN;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    const onc::MatchLayout l = onc::match_layout(n, np);
+    // onc_defragment's buffer, a record or a pending entry where it keeps a
+    // fragment: the slots (under 4 np of them), first_rec and the tile counts
+    // come to under 20.1 bytes per entry + 0.02 per record of its 28 per
+    // fragment.
+    const uint64_t most = std::max<uint64_t>(std::max(n, np), 1);
+    int rc = ensure_defrag(c, most);
+    if (rc != ONC_RC_OK) return rc;
+    if (4 * l.words > defrag_bytes(c->dfr_cap)) return ONC_RC_ENOMEM;     // (not reached: the bound above)
+    onc::MatchArgs a{};
+    a.msgs = msgs;
+    a.status = status;
+    a.rec_conn = rec_conn;
+    a.n = n;
+    a.pending = pending;
+    a.np = np;
+    a.match = match;
+    a.hit = hit;
+    a.tag_out = tag_out;
+    a.still = still;
+    a.result = result;
+    a.variant = c->variant;
+    a.slots = l.slots;
+    a.clear_words = l.clear_words;
+    a.rtiles = l.rtiles;
+    a.ptiles = l.ptiles;
+    a.table = reinterpret_cast<uint32_t*>(c->dfr);
+    a.first_rec = a.table + l.first_rec;
+    a.rec_counts = a.table + l.rec_counts;
+    a.pend_counts = a.table + l.pend_counts;
+    rc = run(c, ONC_K_DEFRAG_PLAN, "match_clear", [&] { return onc::launch_match_clear(a, c->stream); });
+    if (rc == ONC_RC_OK && np)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "match_insert", [&] { return onc::launch_match_insert(a, c->stream); });
+    if (rc == ONC_RC_OK && n)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "match_probe", [&] { return onc::launch_match_probe(a, c->stream); });
+    if (rc == ONC_RC_OK && (n || np))
+        rc = run(c, ONC_K_DEFRAG_PLAN, "match_resolve", [&] { return onc::launch_match_resolve(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "match_scan", [&] { return onc::launch_match_scan(a, c->stream); });
+    if (rc == ONC_RC_OK && np && still)
+        rc = run(c, ONC_K_DEFRAG_COPY, "match_compact", [&] { return onc::launch_match_compact(a, c->stream); });
+    return rc;
+}
+
 int32_t onc_expected_message_len(const uint8_t* data, uint64_t len, uint32_t* out) {
     if (out) *out = 0;
     if (!data || len < 4) return ONC_ERR_INCOMPLETE_HEADER;          // rpc_message.rs:344-346

@@ -13,6 +13,7 @@
 #include "fragment_iov_plan.h"
 #include "fragment_plan.h"
 #include "gather_plan.h"
+#include "match_plan.h"
 #include "payload_plan.h"
 #include "route_plan.h"
 
@@ -295,6 +296,32 @@ struct RouteArgs {
     uint32_t* totals;           // nh + 3
 };
 
+// onc_match_replies (match.hip). Scratch, in onc_defragment's buffer
+// (match_plan.h MatchLayout): the slot table (S words, S a power of two >=
+// 2 np), first_rec (np words), five class counts per tile of records and one
+// unanswered count per tile of pending entries.
+struct MatchArgs {
+    const onc_msg* msgs;        // n, 16-byte aligned
+    const int32_t* status;      // n
+    const uint32_t* rec_conn;   // n, or NULL: connection 0
+    uint64_t n;                 // < ONC_MATCH_MAX
+    const onc_pending* pending; // np, 16-byte aligned
+    uint64_t np;                // < ONC_MATCH_MAX
+    uint32_t* match;            // n
+    uint32_t* hit;              // np
+    uint64_t* tag_out;          // n, optional
+    onc_pending* still;         // np, optional
+    uint64_t* result;           // [6]
+    uint32_t variant;           // ONC_VARIANT_MATCH_ONE_CHAIN
+    uint64_t slots;             // S
+    uint64_t clear_words;       // S + np rounded up to 4: what match_clear fills from `table`
+    uint64_t rtiles, ptiles;    // match_tiles(n), match_tiles(np)
+    uint32_t* table;            // S: a pending index, or kMatchEmpty
+    uint32_t* first_rec;        // np: the lowest record that found the entry, or kMatchEmpty
+    uint32_t* rec_counts;       // kMatchClasses * rtiles (match_class_at)
+    uint32_t* pend_counts;      // ptiles: counted by match_resolve, scanned by match_scan
+};
+
 struct DecArgs {
     uint64_t n;
     const uint8_t* wire;
@@ -463,6 +490,13 @@ hipError_t launch_route_classify(const RouteArgs& a, hipStream_t s);
 hipError_t launch_route_scan_bins(const RouteArgs& a, hipStream_t s);
 hipError_t launch_route_scan_total(const RouteArgs& a, hipStream_t s);
 hipError_t launch_route_scatter(const RouteArgs& a, hipStream_t s);
+// match.hip
+hipError_t launch_match_clear(const MatchArgs& a, hipStream_t s);
+hipError_t launch_match_insert(const MatchArgs& a, hipStream_t s);
+hipError_t launch_match_probe(const MatchArgs& a, hipStream_t s);
+hipError_t launch_match_resolve(const MatchArgs& a, hipStream_t s);
+hipError_t launch_match_scan(const MatchArgs& a, hipStream_t s);
+hipError_t launch_match_compact(const MatchArgs& a, hipStream_t s);
 // streams.hip
 hipError_t launch_streams_chase(const StreamsArgs& a, hipStream_t s);
 hipError_t launch_streams_write(const StreamsArgs& a, hipStream_t s);

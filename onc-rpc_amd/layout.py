@@ -101,6 +101,13 @@ ROUTE_DTYPE = np.dtype({
     "offsets": [0, 4, 8, 12, 16, 20],
     "itemsize": 24,
 })
+# onc_pending (onc_match_replies): a Call waiting for its Reply
+PENDING_DTYPE = np.dtype({
+    "names": ["conn", "xid", "tag"],
+    "formats": ["<u4", "<u4", "<u8"],
+    "offsets": [0, 4, 8],
+    "itemsize": 16,
+})
 
 
 def pack_kind_len(kind, length):

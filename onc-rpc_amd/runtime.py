@@ -48,6 +48,7 @@ EXPORTED = [
     "onc_piece_offsets", "onc_gather_pieces",
     "onc_payload_slots", "onc_place_payloads",
     "onc_route_calls",
+    "onc_match_replies",
 ]
 
 # onc_codec_options (include/onc_rpc.h)
@@ -56,6 +57,7 @@ OPT_FORCE_SCAN = 0x1
 VARIANT_EMIT_WS, VARIANT_EMIT_TILE = 0x200, 0x400
 VARIANT_WS_NO_INTERIOR, VARIANT_WS_NO_FULL, VARIANT_WS_PIPELINE = 0x4000, 0x8000, 0x10000
 VARIANT_EMIT_REPLAN, VARIANT_WHOLE_PLAN = 0x20000, 0x40000
+VARIANT_MATCH_ONE_CHAIN = 0x80000
 # options every Codec() gets unless it is given its own (bench.py --variant)
 DEFAULT_OPTIONS: dict = {}
 
@@ -147,6 +149,7 @@ def load_library(path=LIB_PATH):
     lib.onc_payload_slots.argtypes = [vp, vp, vp, u64, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, vp]
     lib.onc_place_payloads.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp, u64]
     lib.onc_route_calls.argtypes = [vp, vp, vp, u64, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    lib.onc_match_replies.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, vp]
     for name in EXPORTED:
         getattr(lib, name).restype = getattr(lib, name).restype or i32
     # a stale library would read a differently laid out onc_batch and label
@@ -417,6 +420,18 @@ class Codec:
         self._check(self.lib.onc_route_calls(self.h, _ptr(msgs), _ptr(status), n, _ptr(table), ntab, nh, _ptr(route),
                                              _ptr(order), _ptr(bin_first), _ptr(calls_out), _ptr(replies),
                                              _ptr(result)), "onc_route_calls")
+
+    def match_replies(self, msgs, status, rec_conn, n, pending, npend, match, hit, result, tag_out=None, still=None):
+        """onc_match_replies: every decoded record paired with the pending Call
+        (L.PENDING_DTYPE rows) whose (conn, xid) it answers: match[n] (the
+        entry's index or a MATCH_* sentinel), hit[npend] (the record, or
+        MATCH_NONE), optionally the entries' tags per record (tag_out) and the
+        entries still waiting, in list order (still); result = {matched,
+        unknown, duplicate, not_reply, failed, still waiting}. rec_conn may be
+        None: every record on connection 0."""
+        self._check(self.lib.onc_match_replies(self.h, _ptr(msgs), _ptr(status), _ptr(rec_conn), n, _ptr(pending),
+                                               npend, _ptr(match), _ptr(hit), _ptr(tag_out), _ptr(still),
+                                               _ptr(result)), "onc_match_replies")
 
     def frame_streams(self, wire, seg_off, seg_len, nseg, rec_start, rec_len, rec_seg, max_records, seg_result,
                       result):
@@ -977,6 +992,52 @@ def route_calls_host(codec: Codec, msgs, status, table, nh, calls_out=True, repl
             "result": raw["result"][:4],
             "calls_out": None if d_calls is None else raw["calls_out"][:n * 64].view(L.MSG_DTYPE),
             "replies": None if d_rep is None else raw["replies"][:n * 64].view(L.MSG_DTYPE), "raw": raw}
+
+
+MATCH_TILE = 1024           # ONC_MATCH_TILE: records / entries per workgroup of onc_match_replies' kernels
+MATCH_UNKNOWN, MATCH_DUPLICATE, MATCH_NOT_REPLY, MATCH_FAILED = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
+MATCH_NONE, MATCH_MAX = 0xFFFFFFFF, 0xFFFFFFF0
+
+
+def pending_calls(rows):
+    """(conn, xid, tag) rows -> an L.PENDING_DTYPE array, as given."""
+    t = np.zeros(len(rows), L.PENDING_DTYPE)
+    for i, row in enumerate(rows):
+        t[i] = tuple(row)
+    return t
+
+
+def match_replies_host(codec: Codec, msgs, status, rec_conn, pending, tag_out=True, still=True, extra=4,
+                       device="cuda"):
+    """Convenience: host descriptors (L.MSG_DTYPE), statuses, the records'
+    connections (or None) and a pending list (L.PENDING_DTYPE) ->
+    onc_match_replies -> a dict of host arrays: match[n], hit[np], result[6],
+    tag_out[n] (None when not asked for), still[k] (k = result[5]; None when
+    not asked for), and `raw`: the whole output arrays with `extra` elements
+    behind them, pre-filled with sentinels (0xA5 bytes), so that a caller can
+    see what was left alone."""
+    torch = _torch()
+    m = np.ascontiguousarray(msgs, L.MSG_DTYPE)
+    pd = np.ascontiguousarray(pending, L.PENDING_DTYPE)
+    n, npend = len(m), len(pd)
+    d_msgs = to_device(m, device)
+    d_st = _dev_words(status, np.int32, np.int32, device)
+    d_conn = None if rec_conn is None else _dev_words(rec_conn, np.uint32, np.int32, device)
+    d_pend = to_device(pd, device)
+    fill = lambda count, width: torch.full(((count + extra) * width,), 0xA5, dtype=torch.uint8, device=device)
+    match, hit, res = fill(n, 4), fill(npend, 4), fill(6, 8)
+    d_tag = fill(n, 8) if tag_out else None
+    d_still = fill(npend, 16) if still else None
+    codec.match_replies(d_msgs, d_st, d_conn, n, d_pend, npend, match, hit, res, tag_out=d_tag, still=d_still)
+    codec.sync()
+    raw = {"match": match.cpu().numpy().view(np.uint32).copy(), "hit": hit.cpu().numpy().view(np.uint32).copy(),
+           "result": res.cpu().numpy().view(np.uint64).copy(),
+           "tag_out": None if d_tag is None else d_tag.cpu().numpy().view(np.uint64).copy(),
+           "still": None if d_still is None else d_still.cpu().numpy().view(L.PENDING_DTYPE).copy()}
+    k = int(raw["result"][5])
+    return {"match": raw["match"][:n], "hit": raw["hit"][:npend], "result": raw["result"][:6],
+            "tag_out": None if d_tag is None else raw["tag_out"][:n],
+            "still": None if d_still is None else raw["still"][:min(k, npend)], "raw": raw}
 
 
 def place_payloads_host(codec: Codec, wire, frag_start, frag_len, rec_frag, frag_pre, rec_len, pay_pos, pay_len,
