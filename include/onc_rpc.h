@@ -410,7 +410,14 @@ typedef struct onc_codec onc_codec;
 
 /* Kernel-variant bits (onc_codec_options.variant): measurement and test
  * switches that force a kernel the codec would otherwise choose per batch.
- * Results are bit-identical under every combination; production leaves 0. */
+ * Results are bit-identical under every combination; production leaves 0.
+ * ONC_VARIANT_COPY_ONE_GROUP changes no kernel: the copy kernels of
+ * onc_defragment(_extents), onc_fragment, onc_gather_pieces,
+ * onc_place_payloads, onc_fragment_iov and onc_defragment_heads are launched
+ * as one workgroup instead of one per 32 KiB of capacity. They deal their
+ * output tiles out by gridDim.x, so each of the four waves then walks a run
+ * of ceil(tiles / 4) consecutive tiles, which the default grid does only
+ * beyond 64 MiB of output (tests of that walk; slow on anything large). */
 #define ONC_VARIANT_EMIT_WS          0x200u    /* force the wave-specialised enc_emit */
 #define ONC_VARIANT_EMIT_TILE        0x400u    /* force the wave-per-tile enc_emit */
 #define ONC_VARIANT_WS_NO_INTERIOR   0x4000u   /* wave-specialised: no interior spans */
@@ -419,6 +426,7 @@ typedef struct onc_codec onc_codec;
 #define ONC_VARIANT_EMIT_REPLAN      0x20000u  /* wave-per-tile enc_emit re-plans instead of reading the plan's lengths */
 #define ONC_VARIANT_WHOLE_PLAN       0x40000u  /* plan a large batch whole instead of in chunks */
 #define ONC_VARIANT_MATCH_ONE_CHAIN  0x80000u  /* onc_match_replies: every key hashes to slot S - 2 (one wrapping chain) */
+#define ONC_VARIANT_COPY_ONE_GROUP   0x100000u /* the copy kernels run in one workgroup (runs of tiles per wave at test sizes) */
 
 #define ONC_OPT_FORCE_SCAN 0x1u   /* always launch the separate block-scan kernels (tests of that path) */
 

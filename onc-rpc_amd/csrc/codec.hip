@@ -1424,7 +1424,7 @@ static int defragment(onc_codec* c, const uint8_t* wire, const uint64_t* frag_of
     if (rc == ONC_RC_OK)
         rc = run(c, ONC_K_DEFRAG_PLAN, "defrag_place", [&] { return onc::launch_defrag_place(a, c->stream); });
     if (rc != ONC_RC_OK || out_cap == 0) return rc;
-    return run(c, ONC_K_DEFRAG_COPY, "defrag_copy", [&] { return onc::launch_defrag_copy(a, c->stream); });
+    return run(c, ONC_K_DEFRAG_COPY, "defrag_copy", [&] { return onc::launch_defrag_copy(a, c->stream, c->variant); });
 }
 
 int onc_defragment(onc_codec* c, const uint8_t* wire, const uint64_t* frag_off, uint64_t nfrag, uint8_t* out,
@@ -1495,7 +1495,7 @@ int onc_defragment_heads(onc_codec* c, const uint8_t* wire, const uint64_t* frag
     if (rc == ONC_RC_OK)
         rc = run(c, ONC_K_DEFRAG_PLAN, "heads_place", [&] { return onc::launch_heads_place(h, c->stream); });
     if (rc != ONC_RC_OK || max_records == 0) return rc;
-    return run(c, ONC_K_DEFRAG_COPY, "heads_gather", [&] { return onc::launch_heads_gather(h, c->stream); });
+    return run(c, ONC_K_DEFRAG_COPY, "heads_gather", [&] { return onc::launch_heads_gather(h, c->stream, c->variant); });
 }
 
 int onc_fragment(onc_codec* c, const uint8_t* wire, const uint64_t* rec_off, uint64_t n, uint32_t max_frag,
@@ -1535,7 +1535,7 @@ int onc_fragment(onc_codec* c, const uint8_t* wire, const uint64_t* rec_off, uin
     if (rc == ONC_RC_OK)
         rc = run(c, ONC_K_DEFRAG_PLAN, "fragp_apply", [&] { return onc::launch_fragp_apply(a, c->stream); });
     if (rc != ONC_RC_OK || out_cap == 0) return rc;
-    return run(c, ONC_K_DEFRAG_COPY, "frag_copy", [&] { return onc::launch_frag_copy(a, c->stream); });
+    return run(c, ONC_K_DEFRAG_COPY, "frag_copy", [&] { return onc::launch_frag_copy(a, c->stream, c->variant); });
 }
 
 int onc_fragment_iov(onc_codec* c, const onc_iov_rec* iov, uint64_t n, uint32_t max_frag, const uint32_t* rec_max_frag,
@@ -1582,7 +1582,7 @@ int onc_fragment_iov(onc_codec* c, const onc_iov_rec* iov, uint64_t n, uint32_t 
         rc = run(c, ONC_K_DEFRAG_PLAN, "fragiov_apply", [&] { return onc::launch_fragiov_apply(a, c->stream); });
     // a record that takes a piece takes a mark: without room for one of each nothing is written
     if (rc != ONC_RC_OK || max_pieces == 0 || marks_cap < 4) return rc;
-    return run(c, ONC_K_DEFRAG_COPY, "fragiov_fill", [&] { return onc::launch_fragiov_fill(a, c->stream); });
+    return run(c, ONC_K_DEFRAG_COPY, "fragiov_fill", [&] { return onc::launch_fragiov_fill(a, c->stream, c->variant); });
 }
 
 // The checks onc_piece_offsets and onc_gather_pieces share, and the sources.
@@ -1641,7 +1641,7 @@ int onc_gather_pieces(onc_codec* c, const onc_frag_piece* pieces, const uint64_t
     const uintptr_t oa = reinterpret_cast<uintptr_t>(out);
     a.out = reinterpret_cast<uint8_t*>(oa & ~uintptr_t(15));
     a.origin = oa & 15;
-    return run(c, ONC_K_DEFRAG_COPY, "gather_copy", [&] { return onc::launch_gather_copy(a, c->stream); });
+    return run(c, ONC_K_DEFRAG_COPY, "gather_copy", [&] { return onc::launch_gather_copy(a, c->stream, c->variant); });
 }
 
 int onc_payload_slots(onc_codec* c, const onc_msg* msgs, const int32_t* status, uint64_t n, uint32_t head_len,
@@ -1706,7 +1706,7 @@ int onc_place_payloads(onc_codec* c, const uint8_t* wire, const uint64_t* frag_s
     a.out = reinterpret_cast<uint8_t*>(da & ~uintptr_t(15));
     a.origin = da & 15;
     a.dst_cap = dst_cap;
-    return run(c, ONC_K_DEFRAG_COPY, "place_copy", [&] { return onc::launch_place_copy(a, c->stream); });
+    return run(c, ONC_K_DEFRAG_COPY, "place_copy", [&] { return onc::launch_place_copy(a, c->stream, c->variant); });
 }
 
 int onc_route_calls(onc_codec* c, const onc_msg* msgs, const int32_t* status, uint64_t n, const onc_route* table,

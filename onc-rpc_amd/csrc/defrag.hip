@@ -371,11 +371,12 @@ hipError_t launch_defrag_place(const DefragArgs& a, hipStream_t s) {
 
 // The grid covers the capacity (what is written is known on the device
 // only), up to kDfMaxBlocks workgroups; the kernel deals the tiles out.
-hipError_t launch_defrag_copy(const DefragArgs& a, hipStream_t s) {
+hipError_t launch_defrag_copy(const DefragArgs& a, hipStream_t s, uint32_t variant) {
     const uint64_t per_wg = kDfTile * (kDfThreads / 64);
     const uint64_t cap = a.out_cap > ~0ull - 16 - per_wg ? ~0ull - 16 - per_wg : a.out_cap;
     const uint64_t wgs = (a.origin + cap + per_wg - 1) / per_wg;
-    ONC_LAUNCH(defrag_copy_kernel, dim3(uint32_t(wgs < kDfMaxBlocks ? wgs : kDfMaxBlocks)), dim3(kDfThreads), 0, s, a);
+    const uint64_t most = copy_max_groups(variant, kDfMaxBlocks);
+    ONC_LAUNCH(defrag_copy_kernel, dim3(uint32_t(wgs < most ? wgs : most)), dim3(kDfThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -127,10 +127,11 @@ hipError_t launch_heads_place(const HeadsArgs& a, hipStream_t s) {
 
 // The grid covers the slots there can be (how many records the fragments
 // close is known on the device only), up to kDhMaxBlocks workgroups.
-hipError_t launch_heads_gather(const HeadsArgs& a, hipStream_t s) {
+hipError_t launch_heads_gather(const HeadsArgs& a, hipStream_t s, uint32_t variant) {
     const uint64_t slots = a.nfrag < a.max_records ? a.nfrag : a.max_records;
     const uint64_t wgs = (slots * (a.head_len >> 4) + kDhThreads - 1) / kDhThreads;
-    ONC_LAUNCH(heads_gather_kernel, dim3(uint32_t(wgs < kDhMaxBlocks ? wgs : kDhMaxBlocks)), dim3(kDhThreads), 0, s, a);
+    const uint64_t most = copy_max_groups(variant, kDhMaxBlocks);
+    ONC_LAUNCH(heads_gather_kernel, dim3(uint32_t(wgs < most ? wgs : most)), dim3(kDhThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -364,11 +364,12 @@ hipError_t launch_fragp_apply(const FragmentArgs& a, hipStream_t s) {
 
 // The grid covers the capacity (what is written is known on the device
 // only), up to kFgMaxBlocks workgroups; the kernel deals the tiles out.
-hipError_t launch_frag_copy(const FragmentArgs& a, hipStream_t s) {
+hipError_t launch_frag_copy(const FragmentArgs& a, hipStream_t s, uint32_t variant) {
     const uint64_t per_wg = kFgTile * (kFgThreads / 64);
     const uint64_t cap = a.out_cap > ~0ull - 16 - per_wg ? ~0ull - 16 - per_wg : a.out_cap;
     const uint64_t wgs = (a.origin + cap + per_wg - 1) / per_wg;
-    ONC_LAUNCH(frag_copy_kernel, dim3(uint32_t(wgs < kFgMaxBlocks ? wgs : kFgMaxBlocks)), dim3(kFgThreads), 0, s, a);
+    const uint64_t most = copy_max_groups(variant, kFgMaxBlocks);
+    ONC_LAUNCH(frag_copy_kernel, dim3(uint32_t(wgs < most ? wgs : most)), dim3(kFgThreads), 0, s, a);
     return hipGetLastError();
 }
 

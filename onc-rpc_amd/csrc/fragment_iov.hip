@@ -283,11 +283,12 @@ hipError_t launch_fragiov_apply(const FragmentIovArgs& a, hipStream_t s) {
 
 // The grid covers the piece capacity (what is written is known on the device
 // only), up to kFvMaxBlocks workgroups; the kernel deals the tiles out.
-hipError_t launch_fragiov_fill(const FragmentIovArgs& a, hipStream_t s) {
+hipError_t launch_fragiov_fill(const FragmentIovArgs& a, hipStream_t s, uint32_t variant) {
     const uint64_t per_wg = kFvTile * (kFvThreads / 64);
     const uint64_t cap = a.max_pieces > ~0ull - per_wg ? ~0ull - per_wg : a.max_pieces;
     const uint64_t wgs = (cap + per_wg - 1) / per_wg;
-    ONC_LAUNCH(fragiov_fill_kernel, dim3(uint32_t(wgs < kFvMaxBlocks ? wgs : kFvMaxBlocks)), dim3(kFvThreads), 0, s, a);
+    const uint64_t most = copy_max_groups(variant, kFvMaxBlocks);
+    ONC_LAUNCH(fragiov_fill_kernel, dim3(uint32_t(wgs < most ? wgs : most)), dim3(kFvThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -354,11 +354,12 @@ hipError_t launch_gath_empty(const GatherArgs& a, hipStream_t s) {
 
 // The grid covers the window asked for (what of it exists is known on the
 // device only), up to kGaMaxBlocks workgroups; the kernel deals the tiles out.
-hipError_t launch_gather_copy(const GatherArgs& a, hipStream_t s) {
+hipError_t launch_gather_copy(const GatherArgs& a, hipStream_t s, uint32_t variant) {
     const uint64_t per_wg = kGaTile * (kGaThreads / 64);
     const uint64_t cap = a.count > ~0ull - 16 - per_wg ? ~0ull - 16 - per_wg : a.count;
     const uint64_t wgs = (a.origin + cap + per_wg - 1) / per_wg;
-    ONC_LAUNCH(gather_copy_kernel, dim3(uint32_t(wgs < kGaMaxBlocks ? wgs : kGaMaxBlocks)), dim3(kGaThreads), 0, s, a);
+    const uint64_t most = copy_max_groups(variant, kGaMaxBlocks);
+    ONC_LAUNCH(gather_copy_kernel, dim3(uint32_t(wgs < most ? wgs : most)), dim3(kGaThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -452,39 +452,47 @@ hipError_t launch_compact_iov_lens(const onc_iov_rec* iov, const int32_t* status
                                    hipStream_t s);
 hipError_t launch_compact_iov_apply(onc_iov_rec* iov, const int32_t* status, uint64_t n, const uint64_t* new_off,
                                     uint64_t* totals, hipStream_t s);
+// The copy launchers below that take `variant` (the codec's ONC_VARIANT_*
+// bits) launch one workgroup under ONC_VARIANT_COPY_ONE_GROUP instead of up
+// to their kernel's maximum: the kernels deal their tiles (heads_gather: its
+// chunks) out by gridDim.x, so the same code then walks runs of tiles at
+// sizes a test can afford.
+inline uint64_t copy_max_groups(uint32_t variant, uint64_t max_blocks) {
+    return (variant & ONC_VARIANT_COPY_ONE_GROUP) ? 1 : max_blocks;
+}
 // defrag.hip
 // (blk, frag, place: the extents form when a.frag_start is set)
 hipError_t launch_defrag_blk(const DefragArgs& a, hipStream_t s);
 hipError_t launch_defrag_blkscan(const DefragArgs& a, hipStream_t s);
 hipError_t launch_defrag_frag(const DefragArgs& a, hipStream_t s);
 hipError_t launch_defrag_place(const DefragArgs& a, hipStream_t s);
-hipError_t launch_defrag_copy(const DefragArgs& a, hipStream_t s);
+hipError_t launch_defrag_copy(const DefragArgs& a, hipStream_t s, uint32_t variant = 0);
 // defrag_heads.hip
 hipError_t launch_heads_empty(const HeadsArgs& a, hipStream_t s);
 hipError_t launch_heads_place(const HeadsArgs& a, hipStream_t s);
-hipError_t launch_heads_gather(const HeadsArgs& a, hipStream_t s);
+hipError_t launch_heads_gather(const HeadsArgs& a, hipStream_t s, uint32_t variant = 0);
 // fragment.hip
 hipError_t launch_fragp_blk(const FragmentArgs& a, hipStream_t s);
 hipError_t launch_fragp_blkscan(const FragmentArgs& a, hipStream_t s);
 hipError_t launch_fragp_apply(const FragmentArgs& a, hipStream_t s);
-hipError_t launch_frag_copy(const FragmentArgs& a, hipStream_t s);
+hipError_t launch_frag_copy(const FragmentArgs& a, hipStream_t s, uint32_t variant = 0);
 // fragment_iov.hip
 hipError_t launch_fragiov_blk(const FragmentIovArgs& a, hipStream_t s);
 hipError_t launch_fragiov_blkscan(const FragmentIovArgs& a, hipStream_t s);
 hipError_t launch_fragiov_apply(const FragmentIovArgs& a, hipStream_t s);
-hipError_t launch_fragiov_fill(const FragmentIovArgs& a, hipStream_t s);
+hipError_t launch_fragiov_fill(const FragmentIovArgs& a, hipStream_t s, uint32_t variant = 0);
 // gather.hip
 hipError_t launch_gath_blk(const GatherArgs& a, hipStream_t s);
 hipError_t launch_gath_blkscan(const GatherArgs& a, hipStream_t s);
 hipError_t launch_gath_apply(const GatherArgs& a, hipStream_t s);
 hipError_t launch_gath_empty(const GatherArgs& a, hipStream_t s);
-hipError_t launch_gather_copy(const GatherArgs& a, hipStream_t s);
+hipError_t launch_gather_copy(const GatherArgs& a, hipStream_t s, uint32_t variant = 0);
 // payload.hip
 hipError_t launch_pay_blk(const PaySlotsArgs& a, hipStream_t s);
 hipError_t launch_pay_blkscan(const PaySlotsArgs& a, hipStream_t s);
 hipError_t launch_pay_apply(const PaySlotsArgs& a, hipStream_t s);
 hipError_t launch_pay_empty(const PaySlotsArgs& a, hipStream_t s);
-hipError_t launch_place_copy(const PlaceArgs& a, hipStream_t s);
+hipError_t launch_place_copy(const PlaceArgs& a, hipStream_t s, uint32_t variant = 0);
 // route.hip
 hipError_t launch_route_classify(const RouteArgs& a, hipStream_t s);
 hipError_t launch_route_scan_bins(const RouteArgs& a, hipStream_t s);

@@ -473,11 +473,12 @@ hipError_t launch_pay_empty(const PaySlotsArgs& a, hipStream_t s) {
 
 // The grid covers the capacity (how much of it the slots use is known on the
 // device only), up to kPlMaxBlocks workgroups; the kernel deals the tiles out.
-hipError_t launch_place_copy(const PlaceArgs& a, hipStream_t s) {
+hipError_t launch_place_copy(const PlaceArgs& a, hipStream_t s, uint32_t variant) {
     const uint64_t per_wg = kPlTile * (kPlThreads / 64);
     const uint64_t cap = a.dst_cap > ~0ull - 16 - per_wg ? ~0ull - 16 - per_wg : a.dst_cap;
     const uint64_t wgs = (a.origin + cap + per_wg - 1) / per_wg;
-    ONC_LAUNCH(place_copy_kernel, dim3(uint32_t(wgs < kPlMaxBlocks ? wgs : kPlMaxBlocks)), dim3(kPlThreads), 0, s, a);
+    const uint64_t most = copy_max_groups(variant, kPlMaxBlocks);
+    ONC_LAUNCH(place_copy_kernel, dim3(uint32_t(wgs < most ? wgs : most)), dim3(kPlThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -58,6 +58,7 @@ VARIANT_EMIT_WS, VARIANT_EMIT_TILE = 0x200, 0x400
 VARIANT_WS_NO_INTERIOR, VARIANT_WS_NO_FULL, VARIANT_WS_PIPELINE = 0x4000, 0x8000, 0x10000
 VARIANT_EMIT_REPLAN, VARIANT_WHOLE_PLAN = 0x20000, 0x40000
 VARIANT_MATCH_ONE_CHAIN = 0x80000
+VARIANT_COPY_ONE_GROUP = 0x100000   # the copy kernels in one workgroup: runs of tiles per wave at test sizes
 # options every Codec() gets unless it is given its own (bench.py --variant)
 DEFAULT_OPTIONS: dict = {}
 

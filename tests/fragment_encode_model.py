@@ -255,6 +255,42 @@ def tile_record_boundary_stream(origin, seed=67):
     return packed(recs + [FM.opaque(rng.bytes(2500)), FM.reply28(4)])
 
 
+TILE_RUN_FRAG = 1000
+
+
+def _run_body(ln, F=TILE_RUN_FRAG):
+    """The body length of a record whose fragments take `ln` output bytes at
+    max_frag F (None: no record does)."""
+    if ln < 4:
+        return None
+    k = -(-ln // (F + 4))
+    B = ln - 4 * k
+    return B if B >= 0 and max(1, -(-B // F)) == k else None
+
+
+def tile_run_units():
+    """tile_walk_model.Units of frag_copy at max_frag TILE_RUN_FRAG: an entry
+    is a record's fragments (a short one: a bare mark) or, of no output, an
+    extent of 0..3 bytes that is no record. So positions repeat here too: the
+    plan gives such an extent the next record's position."""
+    import tile_walk_model as TW
+    return TW.Units(TILE, (200, 600), 4, lambda ln: ln == 0 or _run_body(ln) is not None)
+
+
+@functools.lru_cache(maxsize=None)
+def tile_run_stream(kind, ntiles, origin, seed=79):
+    """-> (wire, rec_off): tile_walk_model.layout(kind, ntiles, origin) as
+    records for max_frag TILE_RUN_FRAG. The positions of the walk are the
+    model's out_off."""
+    import tile_walk_model as TW
+    entries, _ = TW.layout(kind, ntiles, origin, tile_run_units())
+    rng = np.random.default_rng(seed + ntiles)
+    parts = []
+    for i, (ln, _) in enumerate(entries):
+        parts.append(bytes([0x80]) * (i % 4) if ln == 0 else FM.opaque(rng.bytes(_run_body(ln))))
+    return packed(parts)
+
+
 def non_record_extents(kind, seed=71):
     """(wire, rec_off): extents of 0, 1, 2 and 3 bytes — no records — first,
     last, adjacent and between records ('mixed'), or nothing else ('only')."""

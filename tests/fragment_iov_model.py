@@ -186,6 +186,41 @@ def tile_straddle_stream(t):
     return build([(4, 0)] * (TILE - t) + [(14, 10)] + [(8, 3)] * 5, seed=200 + t)
 
 
+TILE_RUN_F = 7
+
+
+def _run_split(e, i, F=TILE_RUN_F):
+    """(hdr_len, payload_len) of a record of exactly `e` pieces at max_frag F;
+    e == 0: by turns an entry of no bytes and a header too short to be one
+    (ENC_BAD_DESCRIPTOR), neither of which takes a piece."""
+    if e == 0:
+        return (0, 0) if i % 2 == 0 else (1 + i % 3, i % 5)
+    if e == 1:
+        return 4, 0                                  # a bare mark
+    k = e // 2
+    if e % 2 == 0:
+        return 4 + k * F, 0                          # k fragments of header bytes: mark + piece each
+    return 4 + 3, k * F - 3                          # the first fragment holds header and payload bytes
+
+
+def tile_run_units():
+    """tile_walk_model.Units of fragiov_fill: positions count pieces, a tile
+    is TILE of them, and an entry is a record's pieces. Entries of no bytes
+    and bad descriptors take none, so positions repeat here too: the plan
+    gives them the next record's first piece."""
+    import tile_walk_model as TW
+    return TW.Units(TILE, (8, 30), 1)
+
+
+@functools.lru_cache(maxsize=None)
+def tile_run_stream(kind, ntiles):
+    """tile_walk_model.layout(kind, ntiles, 0) in pieces, as entries for
+    max_frag TILE_RUN_F. The positions of the walk are the model's piece_off."""
+    import tile_walk_model as TW
+    entries, _ = TW.layout(kind, ntiles, 0, tile_run_units())
+    return build([_run_split(e, i) for i, (e, _) in enumerate(entries)], seed=800 + ntiles)
+
+
 @functools.lru_cache(maxsize=None)
 def bare_marks_stream(n=3000):
     """`n` bare-mark records of one piece each (512 of them start in one tile,

@@ -448,13 +448,20 @@ def tile_boundary_stream(kind, origin, seed=37):
     """Fragments piled up where an output tile begins (out at `origin` bytes
     past a 16-byte aligned address: tile 1's first byte is out[TILE - origin]).
     A record's first fragment ends right there; then come
-      'search' : 300 empty continuation fragments — more than the staged
-                 window holds before the tile's first byte;
-      'slide'  : 100 empty ones, then 60 of one byte — the window slides to
-                 the tile's first fragment and then holds the tile;
-      'spill'  : 100 empty ones, then 200 of one byte — after sliding, the
-                 tile still has more fragments than the window;
-    and a last fragment of 3000 bytes, between plain records."""
+      'search' : 300 empty continuation fragments;
+      'slide'  : 100 empty ones, then 60 of one byte;
+      'spill'  : 100 empty ones, then 200 of one byte;
+    and a last fragment of 3000 bytes, between plain records.
+
+    The stream is three tiles long, so at the default grid every tile is the
+    first of its wave's run: its first fragment is found by the search in
+    global memory, which steps over the empty ones, and the staged window
+    starts there. What these streams reach is that search landing on the last
+    of many equal positions, and for 'spill' a first tile of more fragments
+    than the window (copied from global memory); 'search' and 'slide' do not
+    take the copy's window-restart branches. tile_run_stream below puts the
+    same pile-ups on a tile that is carried, and tests/test_gpu_tile_runs.py
+    runs them in one workgroup, where they do."""
     rng = np.random.default_rng(seed)
     empties, ones = {"search": (300, 0), "slide": (100, 60), "spill": (100, 200)}[kind]
     at = TILE - origin                       # out offset of tile 1's first byte
@@ -463,6 +470,27 @@ def tile_boundary_stream(kind, origin, seed=37):
     body = rng.bytes(first_body + ones + 3000)
     cuts = [first_body] * (empties + 1) + [first_body + i for i in range(1, ones + 1)]
     return head + fragment(body, cuts) + FM.opaque(rng.bytes(9000)) + FM.reply28(5)
+
+
+def tile_run_stream(kind, ntiles, origin, seed=41):
+    """-> (stream, entries): tile_walk_model.layout(kind, ntiles, origin) as
+    fragments — an entry of no output is an empty continuation fragment, a
+    short one a continuation of one byte, and about every other ordinary entry
+    starts a new record (its four mark bytes count as its output). The
+    positions of the walk are fragment_out_offsets(stream) and the total."""
+    import tile_walk_model as TW
+    entries, _ = TW.layout(kind, ntiles, origin)
+    rng = np.random.default_rng(seed + ntiles)
+    parts, cur = [], None
+    for i, (ln, what) in enumerate(entries):
+        if i == 0 or (what == "fill" and ln >= 4 and rng.random() < 0.5):
+            if cur is not None:
+                parts.append(fragment(rng.bytes(sum(cur)), np.cumsum(cur)[:-1].tolist()))
+            cur = [ln - 4]
+        else:
+            cur.append(ln)
+    parts.append(fragment(rng.bytes(sum(cur)), np.cumsum(cur)[:-1].tolist()))
+    return b"".join(parts), entries
 
 
 def fragments_per_record(buf):

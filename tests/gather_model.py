@@ -171,6 +171,27 @@ def zero_run_list(run):
 
 
 @functools.lru_cache(maxsize=None)
+def tile_run_list(kind, ntiles, origin, seed=90):
+    """-> (pieces, sources): tile_walk_model.layout(kind, ntiles, origin) as
+    pieces from the header and payload sources (the marks source is NULL); the
+    empty ones point anywhere. For a window from 0 into `out` at `origin` past
+    an aligned address the positions of the walk are piece_pos."""
+    import tile_walk_model as TW
+    entries, _ = TW.layout(kind, ntiles, origin)
+    longest = max(ln for ln, _ in entries)
+    src = _sources(seed + ntiles, 0, 700, max(5000, longest + 77))
+    rng = np.random.default_rng(seed + 1 + ntiles)
+    items = []
+    for i, (ln, _) in enumerate(entries):
+        if ln == 0:
+            items.append(((U64, 0, 1 << 40, 123)[i % 4], 0, (0, 1, 2, 7)[i % 4]))
+        else:
+            s = PIECE_HDR if ln <= 600 and i % 2 else PIECE_PAYLOAD
+            items.append((int(rng.integers(0, len(src[s]) - ln + 1)), ln, s))
+    return make_pieces(items), src
+
+
+@functools.lru_cache(maxsize=None)
 def long_piece_list(length=100_000):
     """One piece of `length` bytes (more than 12 tiles) between small ones; the
     piece after it starts on the last byte of a tile."""

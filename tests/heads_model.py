@@ -155,6 +155,50 @@ def gather(model, wire, frag_start, frag_len, r, pos, length):
     return b"".join(out)
 
 
+GATHER_GROUP = 256                  # defrag_heads.hip kDhThreads: chunks per step of one workgroup
+
+
+def stride_steps_stream(nrec=20, head_len=HEAD_FULL, seed=89):
+    """-> (wire, frag_start, frag_len, too_long): `nrec` records whose slots
+    are nrec * head_len / 16 chunks — with 20 at 736 that is 920, four steps
+    of heads_gather's stride loop in one workgroup. By turns a record is one
+    fragment longer than its slot, fragments of 1..40 bytes with empty ones
+    among them (a seam in almost every chunk), shorter than its slot, and
+    empty. Record `too_long` (slots of the third step) is two fragments whose
+    lengths say 2^30 body bytes each: B = 2^31, ONC_ENC_TOO_LONG. The wire
+    holds only their marks — of a fragment the plan reads the first byte, and
+    of a record that is too long the gather reads nothing — so the model for
+    this stream is serial_heads, which takes B from frag_len as the plan does."""
+    rng = np.random.default_rng(seed)
+    too_long = (2 * GATHER_GROUP + 40) * 16 // head_len
+    parts, start, length, pos = [], [], [], 0
+
+    def put(mark, body, declared=None):
+        nonlocal pos
+        parts.append(_BE.pack(mark) + body)
+        start.append(pos)
+        length.append(4 + len(body) if declared is None else declared)
+        pos += 4 + len(body)
+
+    for r in range(nrec):
+        if r == too_long:
+            put(1 << 30, b"", declared=4 + (1 << 30))
+            put(FR.LAST | (1 << 30), b"", declared=4 + (1 << 30))
+            continue
+        which = r % 4
+        if which == 0:
+            lens = [head_len + 100 + r]
+        elif which == 1:
+            lens = rng.choice((0, 1, 2, 3, 5, 17, 40), 120).tolist()
+        elif which == 2:
+            lens = [100, 0, 0, head_len // 2 - 133 + r]
+        else:
+            lens = [0] if r % 8 == 3 else [0, 0, 9, 0]
+        for i, n in enumerate(lens):
+            put((FR.LAST if i == len(lens) - 1 else 0) | n, rng.bytes(n))
+    return b"".join(parts), np.array(start, np.uint64), np.array(length, np.uint32), too_long
+
+
 # ---------------------------------------------------------------------------
 # onc_decode_heads
 # ---------------------------------------------------------------------------

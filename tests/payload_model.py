@@ -176,6 +176,58 @@ def place_stream(seed=61, small=False):
     return b"".join(recs), names
 
 
+def tile_run_records(kind, ntiles, origin, fragmented, seed=83):
+    """tile_walk_model.layout(kind, ntiles, origin) as records whose payload
+    slices, packed at align 1, are the entries (an entry of no output: a
+    record without a payload). -> dict(wire, frag_start, frag_len, rec_frag,
+    frag_pre, rec_len, pay_pos, pay_len); fragmented: every record cut into 1
+    to 5 fragments, an empty one among them now and then; else the identity
+    form (rec_frag = frag_pre = None). The positions of the walk are 0, the
+    slots and 2^64 - 1."""
+    import fragment_model as FR
+    import tile_walk_model as TW
+    entries, _ = TW.layout(kind, ntiles, origin)
+    rng = np.random.default_rng(seed + ntiles)
+    parts, rec_frag, frag_pre, rec_len, pay_pos, pay_len = [], [0], [], [], [], []
+    for i, (ln, _) in enumerate(entries):
+        pre = int(rng.integers(0, 41))
+        body = rng.bytes(pre + ln + int(rng.integers(0, 9)))
+        cuts = []
+        if fragmented and len(body):
+            cuts = sorted(rng.integers(0, len(body) + 1, int(rng.integers(0, 4))).tolist())
+            if cuts and i % 3 == 0:
+                cuts.insert(0, cuts[0])
+        parts.append(FR.fragment(body, cuts))
+        edges = [0] + cuts
+        frag_pre += edges
+        rec_frag.append(rec_frag[-1] + len(edges))
+        rec_len.append(4 + len(body))
+        pay_pos.append(4 + pre if ln else int(rng.integers(0, 50)))
+        pay_len.append(ln)
+    wire = b"".join(parts)
+    fo = FR.frame_fragments(wire)[0]
+    assert len(fo) - 1 == rec_frag[-1]
+    out = {"wire": wire, "frag_start": fo[:-1].copy(), "frag_len": np.diff(fo.astype(np.int64)).astype(np.uint32),
+           "rec_frag": np.array(rec_frag, np.uint64) if fragmented else None,
+           "frag_pre": np.array(frag_pre, np.uint64) if fragmented else None,
+           "rec_len": np.array(rec_len, np.uint32), "pay_pos": np.array(pay_pos, np.uint32),
+           "pay_len": np.array(pay_len, np.uint32)}
+    return out
+
+
+def payload_extent(slot_off, pay_len, dst_cap):
+    """The dst bytes place_copy may write: up to the last record's slice, or
+    dst_cap (payload_plan.h payload_extent)."""
+    n = len(pay_len)
+    return min(int(slot_off[n - 1]) + int(pay_len[n - 1]), dst_cap)
+
+
+def walk_positions(slot_off, n):
+    """What place_copy walks: entry 0 at 0, entry r + 1 at slot_off[r], and the
+    closing entry at 2^64 - 1."""
+    return [0] + [int(x) for x in slot_off[:n]] + [U64]
+
+
 KINDS = ("whole", "mid", "len1", "len15", "len16", "len17", "tail")
 
 

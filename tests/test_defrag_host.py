@@ -75,6 +75,41 @@ def test_timing_ids():
     assert lib.onc_kernel_name(16) == b"?"
 
 
+def test_copy_one_group_switch():
+    """ONC_VARIANT_COPY_ONE_GROUP: the header, the binding and the walk model
+    agree; it is a bit of its own among the variant bits; the ABI and the
+    options struct are what they were; and each of the six copy launchers
+    takes its workgroup limit from copy_max_groups, which gives its kernel's
+    own maximum with the bit clear."""
+    import re
+    import onc_rpc_amd.runtime as R
+    import tile_walk_model as TW
+    hdr = open(os.path.join(ROOT, "include", "onc_rpc.h")).read()
+    assert "#define ONC_VARIANT_COPY_ONE_GROUP   0x%xu" % R.VARIANT_COPY_ONE_GROUP in hdr
+    bits = [int(v, 16) for v in re.findall(r"#define ONC_VARIANT_\w+\s+(0x[0-9a-fA-F]+)u", hdr)]
+    assert R.VARIANT_COPY_ONE_GROUP in bits and len(set(bits)) == len(bits)
+    assert all(b & (b - 1) == 0 for b in bits), "one bit each"
+    assert "#define ONC_RPC_ABI_VERSION 8" in hdr and R.ABI_VERSION == 8
+    assert C.sizeof(R.OncCodecOptions) == 32
+    assert [f[0] for f in R.OncCodecOptions._fields_] == ["size", "flags", "decode_policy", "variant", "enc_chunk",
+                                                          "frame_chunk"]
+    assert TW.ONE_GROUP == 4 and TW.MAX_BLOCKS == 2048
+    csrc = os.path.join(ROOT, "onc-rpc_amd", "csrc")
+    kh = open(os.path.join(csrc, "kernels.h")).read()
+    assert "return (variant & ONC_VARIANT_COPY_ONE_GROUP) ? 1 : max_blocks;" in kh
+    for src, kernel, most in (("defrag.hip", "defrag_copy", "kDfMaxBlocks"), ("fragment.hip", "frag_copy", "kFgMaxBlocks"),
+                              ("gather.hip", "gather_copy", "kGaMaxBlocks"), ("payload.hip", "place_copy", "kPlMaxBlocks"),
+                              ("fragment_iov.hip", "fragiov_fill", "kFvMaxBlocks"),
+                              ("defrag_heads.hip", "heads_gather", "kDhMaxBlocks")):
+        text = open(os.path.join(csrc, src)).read()
+        body = text[text.index(f"hipError_t launch_{kernel}("):]
+        body = body[:body.index("\n}\n")]
+        assert f"const uint64_t most = copy_max_groups(variant, {most});" in body, src
+        assert f"ONC_LAUNCH({kernel}_kernel, dim3(uint32_t(wgs < most ? wgs : most))" in body, src
+        assert f"onc::launch_{kernel}(" in open(os.path.join(csrc, "codec.hip")).read()
+    assert open(os.path.join(csrc, "codec.hip")).read().count("c->stream, c->variant)") == 6
+
+
 def test_plan_arithmetic_extremes():
     """defrag_plan.h compiled by the host compiler into a stand-alone program
     (tests/cpp_defrag/plan_probe.cpp), with the undefined-behaviour sanitizer

@@ -36,15 +36,15 @@ def R():
 
 @pytest.fixture(scope="module")
 def codecs(R):
-    """Codecs by force_scan, made once."""
+    """Codecs by (force_scan, variant bits), made once."""
     import torch
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     made = {}
 
-    def get(force_scan=False):
-        if force_scan not in made:
-            made[force_scan] = R.Codec(0, force_scan=force_scan)
-        return made[force_scan]
+    def get(force_scan=False, variant=0):
+        if (force_scan, variant) not in made:
+            made[force_scan, variant] = R.Codec(0, force_scan=force_scan, variant=variant)
+        return made[force_scan, variant]
 
     yield get
     for c in made.values():
@@ -165,6 +165,20 @@ def test_one_large_record(codecs, R, max_frag):
     # and back through the receive side
     rb, ro, rs, rr, rf = R.reassemble_host_stream(codecs(), got)
     assert rb == wire and np.array_equal(ro, off) and not rs.any() and rf[0] == int(m["result"][0])
+
+
+@pytest.mark.parametrize("max_frag", [7, 8188, 70_001, 100_000])
+def test_one_large_record_in_one_workgroup(codecs, R, max_frag):
+    """The copy launched as one workgroup (ONC_VARIANT_COPY_ONE_GROUP): 13
+    tiles and more, several per wave (tests/test_gpu_tile_runs.py). The same
+    bytes as the default launch, whole and cut by the capacity."""
+    wire, off = E.large_record_stream()
+    one = codecs(variant=R.VARIANT_COPY_ONE_GROUP)
+    for shift, wire_shift in ((1, 0), (16, 3)):
+        assert _frag(R, one, wire, off, max_frag, shift=shift, wire_shift=wire_shift)[1] == \
+            _frag(R, codecs(), wire, off, max_frag, shift=shift)[1]
+    for cap in (50_000, 28):
+        _frag(R, one, wire, off, max_frag, out_cap=cap)
 
 
 # ---------------------------------------------------------------------------

@@ -38,15 +38,15 @@ def R():
 
 @pytest.fixture(scope="module")
 def codecs(R):
-    """Codecs by force_scan, made once."""
+    """Codecs by (force_scan, variant bits), made once."""
     import torch
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     made = {}
 
-    def get(force_scan=False):
-        if force_scan not in made:
-            made[force_scan] = R.Codec(0, force_scan=force_scan)
-        return made[force_scan]
+    def get(force_scan=False, variant=0):
+        if (force_scan, variant) not in made:
+            made[force_scan, variant] = R.Codec(0, force_scan=force_scan, variant=variant)
+        return made[force_scan, variant]
 
     yield get
     for c in made.values():
@@ -180,6 +180,20 @@ def test_one_record_of_many_tiles(codecs, R):
     m = _fiv(R, codecs(), iov, 7)
     assert int(np.diff(m["piece_off"].astype(np.int64)).max()) > 4 * V.TILE
     assert V.gather(m["pieces"], m["marks"], hdr, pay) == E.stream_bytes(E.fragment(wire, off, 7))
+
+
+def test_many_tiles_in_one_workgroup(codecs, R):
+    """The lists of this file that fill more than four tiles, with the fill
+    launched as one workgroup (ONC_VARIANT_COPY_ONE_GROUP): several tiles per
+    wave (tests/test_gpu_tile_runs.py). The same pieces and marks as the
+    default launch, whole and cut by a capacity."""
+    one = codecs(variant=R.VARIANT_COPY_ONE_GROUP)
+    for iov, F in ((V.bare_marks_stream()[0], 16), (V.large_record_stream()[0], 7)):
+        a, b = _fiv(R, one, iov, F), _fiv(R, codecs(), iov, F)
+        assert len(a["pieces"]) > 4 * V.TILE and np.array_equal(a["pieces"], b["pieces"]) and a["marks"] == b["marks"]
+    _fiv(R, one, V.bare_marks_stream()[0], 16, max_pieces=5 * V.TILE + 188)
+    for kw in ({"max_pieces": 3 * V.TILE + 17}, {"marks_cap": 4 * 700 + 2}):
+        _fiv(R, one, V.large_record_stream()[0], 7, **kw)
 
 
 @pytest.mark.parametrize("n", [255, 256, 257, 1025])

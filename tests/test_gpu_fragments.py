@@ -35,15 +35,15 @@ def R():
 
 @pytest.fixture(scope="module")
 def codecs(R):
-    """Codecs by (frame_chunk, force_scan), made once."""
+    """Codecs by (frame_chunk, force_scan, variant bits), made once."""
     import torch
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     made = {}
 
-    def get(chunk=None, force_scan=False):
-        key = (chunk, force_scan)
+    def get(chunk=None, force_scan=False, variant=0):
+        key = (chunk, force_scan, variant)
         if key not in made:
-            made[key] = R.Codec(0, frame_chunk=chunk or 0, force_scan=force_scan)
+            made[key] = R.Codec(0, frame_chunk=chunk or 0, force_scan=force_scan, variant=variant)
         return made[key]
 
     yield get
@@ -227,9 +227,33 @@ def test_copy_shapes(codecs, R, which):
 @pytest.mark.parametrize("kind", ["search", "slide", "spill"])
 def test_copy_fragments_piled_up_at_a_tile_boundary(codecs, R, kind):
     """More fragments than the copy's staged window holds, before and at an
-    output tile's first byte (`out` 1, 0 and 15 bytes past an aligned address)."""
+    output tile's first byte (`out` 1, 0 and 15 bytes past an aligned
+    address). The streams are three tiles long, and the grid has a wave per
+    tile: tile 1 finds its first fragment by the search in global memory,
+    behind all the empty ones, and 'spill' copies it from there. The copy's
+    own ways of getting there from the tile before — searching on from the
+    window's end, sliding the window — are reached only when a wave runs
+    several tiles: tests/test_gpu_tile_runs.py."""
     for shift in (1, 16, 15):
         _defrag(R, codecs(), M.tile_boundary_stream(kind, (GUARD + shift) % 16), shift=shift)
+
+
+def test_copy_of_many_tiles_in_one_workgroup(codecs, R, originals):
+    """The streams of this file that write more than four tiles, with the copy
+    launched as one workgroup (ONC_VARIANT_COPY_ONE_GROUP): every wave runs
+    several tiles. The same bytes as the default launch."""
+    one = codecs(variant=R.VARIANT_COPY_ONE_GROUP)
+    buf = M.shapes_stream("huge")
+    for shift, wire_shift in ((1, 0), (16, 3)):
+        assert _defrag(R, one, buf, shift=shift, wire_shift=wire_shift)[1] == _defrag(R, codecs(), buf, shift=shift)[1]
+    for name, wire, off, _ in originals:
+        frag = M.refragment(wire, off, M.random_cuts(1))
+        m, got = _defrag(R, one, frag)
+        assert got == wire and np.array_equal(m["rec_off"], off), name
+        if name == "synth":
+            assert len(wire) > 64 * M.TILE
+            end = int(off[len(off) // 2])
+            _defrag(R, one, frag, out_cap=end + 3)          # cut in the middle of the batch
 
 
 # ---------------------------------------------------------------------------

@@ -51,6 +51,16 @@ def codec(R):
     c.close()
 
 
+@pytest.fixture(scope="module")
+def one_group(R):
+    """A codec that launches the copy as one workgroup
+    (ONC_VARIANT_COPY_ONE_GROUP): several tiles per wave
+    (tests/test_gpu_tile_runs.py)."""
+    c = R.Codec(0, variant=R.VARIANT_COPY_ONE_GROUP)
+    yield c
+    c.close()
+
+
 def _dev(a):
     """A numpy array's bytes in a device tensor of exactly that size (None: None)."""
     import torch
@@ -266,6 +276,23 @@ def test_zero_length_runs(codec, R, run):
 
 def test_one_piece_of_many_tiles(codec, R):
     _generic(R, codec, *G.long_piece_list())
+
+
+def test_many_tiles_in_one_workgroup(codec, one_group, R, windows_list):
+    """The lists of this file that are longer than four tiles — one piece of
+    13 tiles and the 6-tile list of the window tests — with the copy launched
+    as one workgroup: the same bytes as the default launch."""
+    pieces, sources = G.long_piece_list()
+    lst = _generic(R, one_group, pieces, sources, shifts=(0, 5, 15))
+    assert lst.total > 12 * G.TILE
+    ref = Listed(R, codec, pieces, sources)
+    assert np.array_equal(lst.window(0, lst.total, 1), ref.window(0, lst.total, 1))
+    ref = windows_list
+    lst = Listed(R, one_group, ref.pieces, ref.sources)
+    for start, count in ((0, ref.total), (1, ref.total), (8185, 5 * G.TILE + 15), (G.TILE, ref.total),
+                         (ref.total - 5 * G.TILE - 50, 5 * G.TILE + 150)):
+        for shift in (0, 3):
+            assert np.array_equal(lst.window(start, count, shift), ref.window(start, count, shift))
 
 
 def test_alignment_grid(codec, R):

@@ -195,6 +195,30 @@ def test_place_fragmented_against_the_model(R, codec, placed_stream, order):
     _place(R, codec, wire, start, flen, h, pay_pos, pay_len, slots, int(slots[n]) + 300000, 7)
 
 
+def test_place_fragmented_in_one_workgroup(R, placed_stream):
+    """The same stream with the copy launched as one workgroup
+    (ONC_VARIANT_COPY_ONE_GROUP): its slots fill more than four tiles, so
+    every wave runs several (tests/test_gpu_tile_runs.py). Against the model,
+    as the default launch above."""
+    wire, start, flen, h, pay_pos, pay_len, names = placed_stream["shuffled"]
+    n = len(pay_len)
+    one = R.Codec(0, variant=R.VARIANT_COPY_ONE_GROUP)
+    try:
+        for slots, cap in [(PM.pack_slots(pay_len, a), None) for a in (1, 4096)] + [PM.odd_slots(pay_len)]:
+            cap = int(slots[n]) if cap is None else max(int(slots[r]) + int(pay_len[r]) for r in range(n))
+            assert cap > 4 * PM.TILE
+            for shift in (0, 15):
+                done = _place(R, one, wire, start, flen, h, pay_pos, pay_len, slots, cap, shift)
+                assert done == np.nonzero(pay_len)[0].tolist()
+        # cut by dst_cap in the middle of the long record's slot, and of a tile
+        slots = PM.pack_slots(pay_len, 16)
+        cap = int(slots[names["long"]]) + 2 * PM.TILE + 1000
+        done = _place(R, one, wire, start, flen, h, pay_pos, pay_len, slots, cap, 9)
+        assert done == [r for r in np.nonzero(pay_len)[0].tolist() if r < names["long"]]
+    finally:
+        one.close()
+
+
 # ---------------------------------------------------------------------------
 # 3. slices that are not OK
 # ---------------------------------------------------------------------------
