@@ -96,7 +96,10 @@ extern "C" {
  *    Calls dispatched to handlers on the device), which adds no status code
  *    and reuses onc_defragment's timing ids; onc_match_replies with
  *    onc_pending (decoded Replies paired with pending Calls on the device),
- *    which adds no status code and reuses onc_defragment's timing ids. */
+ *    which adds no status code and reuses onc_defragment's timing ids;
+ *    onc_group_by_conn and onc_conn_extents (a send batch grouped by
+ *    connection on the device), which add no status code and reuse
+ *    onc_defragment's timing ids. */
 #define ONC_RPC_ABI_VERSION 8
 
 /* ------------------------------------------------------------------------ */
@@ -476,7 +479,9 @@ int onc_codec_sync(onc_codec* codec);
  * onc_match_replies of up to max_records records against up to max_records
  * pending entries builds its slot table, first_rec and tile counts there too
  * (under 32 bytes per pending entry plus under 1 byte per 32 records): a
- * reserve of max(n, np) covers the call. */
+ * reserve of max(n, np) covers the call. onc_group_by_conn of up to
+ * max_records items keeps its digit counts and two (key, index) buffers there
+ * (17 bytes per item and 7 KiB); onc_conn_extents needs no scratch. */
 int onc_codec_reserve(onc_codec* codec, uint64_t max_records);
 /* Map a caller's host buffer (a socket buffer: any malloc'd or mmap'd
  * range) for the kernels, so that an encode / decode reads and writes it in
@@ -554,7 +559,12 @@ int onc_abi_version(void);
  * onc_match_replies reports its clear, insert, probe, resolve and scan
  * launches (match_clear, match_insert, match_probe, match_resolve,
  * match_scan) under ONC_K_DEFRAG_PLAN and its compaction (match_compact)
- * under ONC_K_DEFRAG_COPY. */
+ * under ONC_K_DEFRAG_COPY. onc_group_by_conn reports its counts, scans,
+ * bounds and result (group_count, group_scan_digits, group_scan_total,
+ * group_bounds, group_result) under ONC_K_DEFRAG_PLAN and its scatters and
+ * gather (group_identity, group_scatter, group_gather) under
+ * ONC_K_DEFRAG_COPY; onc_conn_extents' one launch reports under
+ * ONC_K_DEFRAG_PLAN. */
 #define ONC_K_ENC_LEN      0
 #define ONC_K_SCAN_TILES   1
 #define ONC_K_ENC_EMIT     2
@@ -1647,6 +1657,102 @@ int onc_match_replies(onc_codec* codec, const onc_msg* msgs, const int32_t* stat
                       uint64_t* tag_out     /*[dev, n], optional*/,
                       onc_pending* still    /*[dev, np], optional*/,
                       uint64_t* result      /*[dev, 6]*/);
+
+/* onc_route_calls leaves the reply descriptors in handler order and onc_encode
+ * serialises them in that order; a server sends per connection, one socket
+ * each, and a client's Calls are built in whatever order the application
+ * produced them. onc_group_by_conn is the step between: a stable sort of the
+ * item indices by connection id, the start of every connection's run, and
+ * optionally the descriptors gathered into that order, so that onc_encode's
+ * output is one contiguous stream per connection (onc_conn_extents: where). */
+#define ONC_GROUP_CONN_MAX 0x00FFFFFFu   /* nconn at most 2^24 - 1 */
+#define ONC_GROUP_TILE     1024u         /* items per workgroup (tests: the sizes around it) */
+
+/* onc_group_by_conn. The result is exactly that of
+ *
+ *   for k in 0 .. n-1:
+ *       s = via ? via[k] : k
+ *       c = s < nsrc ? rec_conn[s] : nconn       # an index outside rec_conn is never read
+ *       key[k] = min(c, nconn)                   # group nconn: "no connection", nothing to send
+ *   order = the item indices 0 .. n-1 sorted by key[], stably (ascending k inside a group)
+ *   conn_first[c] = number of items with key < c, for c in 0 .. nconn+1
+ *                   # group c is order[conn_first[c] .. conn_first[c+1]); conn_first[nconn+1] == n
+ *   if msgs_out: msgs_out[j] = msgs[order[j]]    # all 64 bytes, untouched; msgs is indexed by item, not through via
+ *   result = {conn_first[nconn], n - conn_first[nconn], number of c < nconn with a non-empty group}
+ *
+ *  - Server: rec_conn = onc_frame_streams' rec_seg, via = onc_route_calls'
+ *    order, n = bin_first[nh + 1] (the Calls, served and rejected: the last
+ *    two bins have zero replies), msgs = replies after the handlers filled
+ *    their slices. msgs_out[0 .. result[0]) is then an onc_batch.msgs that
+ *    onc_encode serialises as it stands; connection c's stream is the records
+ *    [conn_first[c], conn_first[c+1]) of it, in the items' order: handler by
+ *    handler and, inside a handler, in the order the connection sent its
+ *    Calls (a peer pairs a Reply with its Call by xid, not by position). A
+ *    writev sender takes the same slice of onc_encode_iov's entries.
+ *  - Client: via NULL, rec_conn = the connection per Call; `order` carries the
+ *    caller's onc_pending list into the same order.
+ *  - A connection id of nconn or more (0xFFFFFFFF for instance) marks an item
+ *    that is not sent: those come last, in group nconn.
+ *  - The checks come before anything is launched, pointers before alignment.
+ *    ONC_RC_EINVAL: a NULL codec, result or conn_first; nconn >
+ *    ONC_GROUP_CONN_MAX; n >= 2^32 (an order entry is 32 bits); with via NULL,
+ *    nsrc != n; with n > 0 a NULL order; with n > 0 and nsrc > 0 a NULL
+ *    rec_conn; msgs_out without msgs; msgs_out == msgs; order == via (a
+ *    permutation cannot be done in place). ONC_RC_EALIGN: msgs or msgs_out not
+ *    16-byte aligned, conn_first or result not 8-byte aligned, rec_conn, via
+ *    or order not 4-byte aligned. n == 0 still writes conn_first (zeros) and
+ *    result. nconn == 0 is valid: everything is group 0 and order is the
+ *    identity.
+ * The call is asynchronous on the codec's stream and every step is a kernel
+ * launch (no memset or memcpy node: a captured call replays); how many depends
+ * on n and nconn only. Every caller array is read and written with plain loads
+ * and stores only, so any of them may be mapped host memory; all atomics go to
+ * LDS. Scratch: the tiles' digit counts and two (key, index) buffers, 17 bytes
+ * per item and 7 KiB, in onc_defragment's buffer: onc_codec_reserve(
+ * max_records >= n) covers it; growing it inside a capture is
+ * ONC_RC_ECAPTURE. The counts, scans, bounds and result launches report under
+ * ONC_K_DEFRAG_PLAN, the scatters and the gather under ONC_K_DEFRAG_COPY.
+ * Kernels (group.hip), the launch boundary being the only barrier between
+ * workgroups: a least-significant-digit radix sort of (key, index) pairs with
+ * 8-bit digits, passes = ceil(bits(nconn) / 8) with bits(0) = 0, so 0 to 3.
+ * Without a pass group_identity writes order. Per pass: group_count (a
+ * workgroup per tile of ONC_GROUP_TILE items; the first pass reads rec_conn
+ * through via and clamps, later passes read the pairs in sequence; a digit's
+ * peers in a wave found with one ballot per digit bit; the tile's counts go to
+ * the scratch digit-major), group_scan_digits (a workgroup per digit: its tile
+ * counts scanned in place), group_scan_total (the 256 totals scanned),
+ * group_scatter (every item ranked stably — inside a wave by the ballots,
+ * across waves by per-wave counts added in wave order — and its pair written
+ * there; the last pass writes order). Then group_bounds (a lane per entry of
+ * conn_first: a lower-bound binary search of the sorted keys, 32 dependent
+ * loads at most, and the non-empty groups counted per workgroup), group_result
+ * (one workgroup: those counts summed; result) and, with msgs_out,
+ * group_gather (four consecutive lanes on the four 16-byte pieces of a
+ * descriptor: a wave's stores are whole lines). Every index that addresses
+ * memory is 64-bit. */
+int onc_group_by_conn(onc_codec* codec,
+                      const uint32_t* rec_conn /*[dev, nsrc]*/, uint64_t nsrc,
+                      const uint32_t* via      /*[dev, n], optional*/,
+                      uint64_t n, uint32_t nconn,
+                      uint32_t* order          /*[dev, n]*/,
+                      uint64_t* conn_first     /*[dev, nconn + 2]*/,
+                      const onc_msg* msgs      /*[dev, n], optional*/,
+                      onc_msg* msgs_out        /*[dev, n], optional; needs msgs*/,
+                      uint64_t* result         /*[dev, 3]*/);
+
+/* onc_conn_extents: conn_off[c] = rec_off[min(conn_first[c], nrec)] for c in
+ * 0 .. nconn+1: connection c's bytes of the encoded stream are
+ * out[conn_off[c], conn_off[c+1]). rec_off is any nrec + 1 offsets:
+ * onc_encode's, its offsets after onc_compact, or onc_fragment's out_off. A
+ * caller that encoded only the first result[0] descriptors passes that as
+ * nrec: the clamp keeps the dropped group's entries inside rec_off, and
+ * nothing outside it is ever read. One kernel with a lane per entry
+ * (ONC_K_DEFRAG_PLAN), no scratch. ONC_RC_EINVAL: a NULL codec, rec_off,
+ * conn_first or conn_off; nconn > ONC_GROUP_CONN_MAX. ONC_RC_EALIGN: a
+ * pointer that is not 8-byte aligned. */
+int onc_conn_extents(onc_codec* codec, const uint64_t* rec_off /*[dev, nrec + 1]*/, uint64_t nrec,
+                     const uint64_t* conn_first /*[dev, nconn + 2]*/, uint32_t nconn,
+                     uint64_t* conn_off /*[dev, nconn + 2]*/);
 
 /* Exclusive scan of record lengths into offsets:
  * rec_off[0] = base, rec_off[i+1] = rec_off[i] + rec_len[i]  ([dev]). */

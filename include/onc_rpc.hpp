@@ -2305,6 +2305,101 @@ inline MatchedReplies match_replies(Codec& codec, const std::vector<Decoded>& re
     return out;
 }
 
+// ---------------------------------------------------------------------------
+// A send batch grouped by connection (onc_group_by_conn, onc_conn_extents)
+// ---------------------------------------------------------------------------
+// What group_by_conn returns: the items sorted stably by connection, as
+// positions in `order`; connection c's items are order[conn_first[c] ..
+// conn_first[c + 1]), in the order they were given, and the items of no
+// connection (an id of nconn or more) come last. msgs[j] is the descriptor of
+// item order[j] when descriptors were given: msgs[0 .. n_sent) encodes as it
+// stands into one contiguous stream per connection.
+struct GroupedSends {
+    struct Span {
+        const uint32_t* index = nullptr;   // n positions in the batch as given
+        const onc_msg* msgs = nullptr;     // their descriptors, or nullptr
+        size_t n = 0;
+    };
+    uint32_t nconn = 0;
+    std::vector<uint32_t> order;           // n
+    std::vector<uint64_t> conn_first;      // nconn + 2
+    std::vector<onc_msg> msgs;             // n, or empty
+    size_t n_sent = 0, n_dropped = 0, n_active = 0;
+
+    Span group(uint32_t g) const {
+        const size_t lo = size_t(conn_first[g]);
+        return Span{order.data() + lo, msgs.empty() ? nullptr : msgs.data() + lo, size_t(conn_first[g + 1]) - lo};
+    }
+    Span of(uint32_t c) const {
+        if (c >= nconn) throw CodecError("GroupedSends: no such connection");
+        return group(c);
+    }
+    Span dropped() const { return group(nconn); }
+    size_t active() const { return n_active; }     // connections with an item
+
+    // onc_conn_extents: connection c's bytes of the stream that msgs[0 ..
+    // nrec) encoded to with the offsets rec_off (nrec + 1 of them: the whole
+    // batch, or only its first n_sent records) are [first, second) of entry
+    // c; entry nconn is the dropped group's range (empty when those were not
+    // encoded).
+    std::vector<std::pair<uint64_t, uint64_t>> connection_streams(Codec& codec, const std::vector<uint64_t>& rec_off) const {
+        using detail::need;
+        if (rec_off.empty()) throw CodecError("connection_streams: rec_off holds nrec + 1 offsets");
+        const size_t ne = size_t(nconn) + 2;
+        detail::Carve c{codec.stage(need<uint64_t>(rec_off.size()) + 2 * need<uint64_t>(ne))};
+        const auto ro = c.take<uint64_t>(rec_off.size());
+        const auto cf = c.take<uint64_t>(ne);
+        const auto co = c.take<uint64_t>(ne);
+        std::memcpy(ro.host, rec_off.data(), 8 * rec_off.size());
+        std::memcpy(cf.host, conn_first.data(), 8 * ne);
+        codec.check(onc_conn_extents(codec.get(), ro.dev, rec_off.size() - 1, cf.dev, nconn, co.dev), "onc_conn_extents");
+        codec.sync();
+        std::vector<std::pair<uint64_t, uint64_t>> out(size_t(nconn) + 1);
+        for (size_t g = 0; g <= nconn; ++g) out[g] = {co.host[g], co.host[g + 1]};
+        return out;
+    }
+};
+
+// onc_group_by_conn: item k goes out on connection conn_of[via[k]] (an empty
+// `via`: conn_of[k]); an id of nconn or more, or an index outside conn_of,
+// marks an item that is not sent. `msgs`, when given, holds a descriptor per
+// item and comes back in connection order. Inputs and outputs go through the
+// codec's stage; one synchronisation.
+inline GroupedSends group_by_conn(Codec& codec, const std::vector<uint32_t>& conn_of, const std::vector<uint32_t>& via,
+                                  uint32_t nconn, const std::vector<onc_msg>& msgs = {}) {
+    using detail::need;
+    const size_t nsrc = conn_of.size(), n = via.empty() ? nsrc : via.size();
+    if (nconn > ONC_GROUP_CONN_MAX) throw CodecError("group_by_conn: too many connections");
+    if (n >= (uint64_t(1) << 32)) throw CodecError("group_by_conn: too many items");
+    if (!msgs.empty() && msgs.size() != n) throw CodecError("group_by_conn: a descriptor per item");
+    const size_t nm = msgs.size(), ne = size_t(nconn) + 2;
+    detail::Carve c{codec.stage(need<uint32_t>(nsrc) + 2 * need<uint32_t>(n) + need<uint64_t>(ne) + 2 * need<onc_msg>(nm) +
+                                need<uint64_t>(3))};
+    const auto rc = c.take<uint32_t>(nsrc);
+    const auto vi = c.take<uint32_t>(via.size());
+    const auto od = c.take<uint32_t>(n);
+    const auto cf = c.take<uint64_t>(ne);
+    const auto mi = c.take<onc_msg>(nm);
+    const auto mo = c.take<onc_msg>(nm);
+    const auto res = c.take<uint64_t>(3);
+    if (nsrc) std::memcpy(rc.host, conn_of.data(), 4 * nsrc);
+    if (!via.empty()) std::memcpy(vi.host, via.data(), 4 * via.size());
+    if (nm) std::memcpy(mi.host, msgs.data(), sizeof(onc_msg) * nm);
+    codec.check(onc_group_by_conn(codec.get(), rc.dev, nsrc, via.empty() ? nullptr : vi.dev, n, nconn, od.dev, cf.dev,
+                                  nm ? mi.dev : nullptr, nm ? mo.dev : nullptr, res.dev),
+                "onc_group_by_conn");
+    codec.sync();
+    GroupedSends out;
+    out.nconn = nconn;
+    out.order.assign(od.host, od.host + n);
+    out.conn_first.assign(cf.host, cf.host + ne);
+    if (nm) out.msgs.assign(mo.host, mo.host + nm);
+    out.n_sent = size_t(res.host[0]);
+    out.n_dropped = size_t(res.host[1]);
+    out.n_active = size_t(res.host[2]);
+    return out;
+}
+
 inline FragmentedHeads BatchDecoder::try_from_fragmented_heads(Codec& codec, const uint8_t* wire, size_t wire_len,
                                                                const std::vector<Segment>& segments, DecodeMode mode,
                                                                uint32_t head_len) {

@@ -1816,6 +1816,91 @@ int onc_match_replies(onc_codec* c, const onc_msg* msgs, const int32_t* status, 
     return rc;
 }
 
+int onc_group_by_conn(onc_codec* c, const uint32_t* rec_conn, uint64_t nsrc, const uint32_t* via, uint64_t n,
+                      uint32_t nconn, uint32_t* order, uint64_t* conn_first, const onc_msg* msgs, onc_msg* msgs_out,
+                      uint64_t* result) {
+    if (!c || !result || !conn_first) return ONC_RC_EINVAL;
+    if (nconn > ONC_GROUP_CONN_MAX || n >= (1ull << 32)) return ONC_RC_EINVAL;
+    if (!via && nsrc != n) return ONC_RC_EINVAL;
+    if (n && !order) return ONC_RC_EINVAL;
+    if (n && nsrc && !rec_conn) return ONC_RC_EINVAL;
+    if (msgs_out && (!msgs || msgs_out == msgs)) return ONC_RC_EINVAL;
+    // a permutation cannot be done in place
+    if (order && order == via) return ONC_RC_EINVAL;
+    const auto low = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (low(msgs, 15) || low(msgs_out, 15) || low(conn_first, 7) || low(result, 7) || low(rec_conn, 3) ||
+        low(via, 3) || low(order, 3))
+        return ONC_RC_EALIGN;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    // onc_defragment's buffer, an item where it keeps a fragment: two (key,
+    // index) buffers and the digit counts, 17 n + 7216 bytes of its 28 per
+    // fragment (for at least 65536 of them: ensure_defrag's floor).
+    int rc = ensure_defrag(c, n ? n : 1);
+    if (rc != ONC_RC_OK) return rc;
+    const onc::GroupLayout l = onc::group_layout(n, onc::kGroupTile);
+    static_assert(17ull * 65536 + 7216 <= 28ull * 65536, "the scratch of a batch below the floor fits the floor");
+    if (4 * l.words > defrag_bytes(c->dfr_cap)) return ONC_RC_ENOMEM;     // (not reached: the bound above)
+    uint32_t* const w = reinterpret_cast<uint32_t*>(c->dfr);
+    onc::GroupArgs a{};
+    a.rec_conn = rec_conn;
+    a.nsrc = nsrc;
+    a.via = via;
+    a.n = n;
+    a.nconn = nconn;
+    a.passes = n ? onc::group_passes(nconn) : 0;
+    a.order = order;
+    a.conn_first = conn_first;
+    a.msgs = msgs;
+    a.msgs_out = msgs_out;
+    a.result = result;
+    a.tiles = onc::group_tiles(n, onc::kGroupTile);
+    a.counts = w + l.counts;
+    a.totals = w + l.totals;
+    a.first = w + l.first;
+    a.partial = w + l.partial;
+    a.bounds_groups = onc::group_bounds_groups(nconn);
+    if (n && a.passes == 0)
+        rc = run(c, ONC_K_DEFRAG_COPY, "group_identity", [&] { return onc::launch_group_identity(a, c->stream); });
+    const uint32_t bits = onc::group_bits(nconn);
+    for (uint32_t p = 0; p < a.passes && rc == ONC_RC_OK; ++p) {
+        const uint32_t d = onc::group_pass_dst(p);
+        a.pass = p;
+        a.digit_bits = std::min<uint32_t>(onc::kGroupDigitBits, bits - onc::kGroupDigitBits * p);
+        a.src_key = w + l.key[d ^ 1];
+        a.src_idx = w + l.idx[d ^ 1];
+        a.dst_key = w + l.key[d];
+        a.dst_idx = p + 1 == a.passes ? order : w + l.idx[d];
+        a.sorted_key = a.dst_key;
+        rc = run(c, ONC_K_DEFRAG_PLAN, "group_count", [&] { return onc::launch_group_count(a, c->stream); });
+        if (rc == ONC_RC_OK)
+            rc = run(c, ONC_K_DEFRAG_PLAN, "group_scan_digits",
+                     [&] { return onc::launch_group_scan_digits(a, c->stream); });
+        if (rc == ONC_RC_OK)
+            rc = run(c, ONC_K_DEFRAG_PLAN, "group_scan_total", [&] { return onc::launch_group_scan_total(a, c->stream); });
+        if (rc == ONC_RC_OK)
+            rc = run(c, ONC_K_DEFRAG_COPY, "group_scatter", [&] { return onc::launch_group_scatter(a, c->stream); });
+    }
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "group_bounds", [&] { return onc::launch_group_bounds(a, c->stream); });
+    if (rc == ONC_RC_OK)
+        rc = run(c, ONC_K_DEFRAG_PLAN, "group_result", [&] { return onc::launch_group_result(a, c->stream); });
+    if (rc == ONC_RC_OK && n && msgs_out)
+        rc = run(c, ONC_K_DEFRAG_COPY, "group_gather", [&] { return onc::launch_group_gather(a, c->stream); });
+    return rc;
+}
+
+int onc_conn_extents(onc_codec* c, const uint64_t* rec_off, uint64_t nrec, const uint64_t* conn_first, uint32_t nconn,
+                     uint64_t* conn_off) {
+    if (!c || !rec_off || !conn_first || !conn_off) return ONC_RC_EINVAL;
+    if (nconn > ONC_GROUP_CONN_MAX) return ONC_RC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(rec_off) & 7) || (reinterpret_cast<uintptr_t>(conn_first) & 7) ||
+        (reinterpret_cast<uintptr_t>(conn_off) & 7))
+        return ONC_RC_EALIGN;
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    return run(c, ONC_K_DEFRAG_PLAN, "conn_extents",
+               [&] { return onc::launch_conn_extents(rec_off, nrec, conn_first, nconn, conn_off, c->stream); });
+}
+
 int32_t onc_expected_message_len(const uint8_t* data, uint64_t len, uint32_t* out) {
     if (out) *out = 0;
     if (!data || len < 4) return ONC_ERR_INCOMPLETE_HEADER;          // rpc_message.rs:344-346

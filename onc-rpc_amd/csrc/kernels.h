@@ -13,6 +13,7 @@
 #include "fragment_iov_plan.h"
 #include "fragment_plan.h"
 #include "gather_plan.h"
+#include "group_plan.h"
 #include "match_plan.h"
 #include "payload_plan.h"
 #include "route_plan.h"
@@ -322,6 +323,37 @@ struct MatchArgs {
     uint32_t* pend_counts;      // ptiles: counted by match_resolve, scanned by match_scan
 };
 
+// onc_group_by_conn (group.hip). Scratch, in onc_defragment's buffer
+// (group_plan.h GroupLayout): the tiles' digit counts, a total and a first
+// position per digit, the bounds kernel's partial counts and two (key, index)
+// buffers — 17 bytes per item.
+struct GroupArgs {
+    const uint32_t* rec_conn;   // nsrc
+    uint64_t nsrc;
+    const uint32_t* via;        // n, or NULL: item k is rec_conn[k]
+    uint64_t n;                 // < 2^32
+    uint32_t nconn;             // <= ONC_GROUP_CONN_MAX
+    uint32_t passes;            // group_passes(nconn)
+    uint32_t pass;              // the launch's pass
+    uint32_t digit_bits;        // bits of its digit that can be set
+    uint32_t* order;            // n
+    uint64_t* conn_first;       // nconn + 2
+    const onc_msg* msgs;        // n, optional
+    onc_msg* msgs_out;          // n, optional
+    uint64_t* result;           // [3]
+    uint64_t tiles;             // group_tiles(n, kGroupTile)
+    uint32_t* counts;           // kGroupDigits * tiles (group_count_at)
+    uint32_t* totals;           // kGroupDigits
+    uint32_t* first;            // kGroupDigits
+    uint32_t* partial;          // bounds_groups
+    uint32_t bounds_groups;     // workgroups of group_bounds
+    const uint32_t* src_key;    // n: what a pass after the first reads
+    const uint32_t* src_idx;
+    uint32_t* dst_key;          // n: what the pass writes
+    uint32_t* dst_idx;          // (the last pass: order)
+    const uint32_t* sorted_key; // n: the last pass's keys
+};
+
 struct DecArgs {
     uint64_t n;
     const uint8_t* wire;
@@ -498,6 +530,18 @@ hipError_t launch_route_classify(const RouteArgs& a, hipStream_t s);
 hipError_t launch_route_scan_bins(const RouteArgs& a, hipStream_t s);
 hipError_t launch_route_scan_total(const RouteArgs& a, hipStream_t s);
 hipError_t launch_route_scatter(const RouteArgs& a, hipStream_t s);
+// group.hip
+uint32_t group_bounds_groups(uint32_t nconn);
+hipError_t launch_group_identity(const GroupArgs& a, hipStream_t s);
+hipError_t launch_group_count(const GroupArgs& a, hipStream_t s);
+hipError_t launch_group_scan_digits(const GroupArgs& a, hipStream_t s);
+hipError_t launch_group_scan_total(const GroupArgs& a, hipStream_t s);
+hipError_t launch_group_scatter(const GroupArgs& a, hipStream_t s);
+hipError_t launch_group_bounds(const GroupArgs& a, hipStream_t s);
+hipError_t launch_group_result(const GroupArgs& a, hipStream_t s);
+hipError_t launch_group_gather(const GroupArgs& a, hipStream_t s);
+hipError_t launch_conn_extents(const uint64_t* rec_off, uint64_t nrec, const uint64_t* conn_first, uint32_t nconn,
+                               uint64_t* conn_off, hipStream_t s);
 // match.hip
 hipError_t launch_match_clear(const MatchArgs& a, hipStream_t s);
 hipError_t launch_match_insert(const MatchArgs& a, hipStream_t s);

@@ -49,6 +49,7 @@ EXPORTED = [
     "onc_payload_slots", "onc_place_payloads",
     "onc_route_calls",
     "onc_match_replies",
+    "onc_group_by_conn", "onc_conn_extents",
 ]
 
 # onc_codec_options (include/onc_rpc.h)
@@ -151,6 +152,8 @@ def load_library(path=LIB_PATH):
     lib.onc_place_payloads.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp, u64]
     lib.onc_route_calls.argtypes = [vp, vp, vp, u64, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
     lib.onc_match_replies.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, vp]
+    lib.onc_group_by_conn.argtypes = [vp, vp, u64, vp, u64, C.c_uint32, vp, vp, vp, vp, vp]
+    lib.onc_conn_extents.argtypes = [vp, vp, u64, vp, C.c_uint32, vp]
     for name in EXPORTED:
         getattr(lib, name).restype = getattr(lib, name).restype or i32
     # a stale library would read a differently laid out onc_batch and label
@@ -433,6 +436,25 @@ class Codec:
         self._check(self.lib.onc_match_replies(self.h, _ptr(msgs), _ptr(status), _ptr(rec_conn), n, _ptr(pending),
                                                npend, _ptr(match), _ptr(hit), _ptr(tag_out), _ptr(still),
                                                _ptr(result)), "onc_match_replies")
+
+    def group_by_conn(self, rec_conn, nsrc, via, n, nconn, order, conn_first, result, msgs=None, msgs_out=None):
+        """onc_group_by_conn: item k's connection is rec_conn[via[k]] (via
+        None: rec_conn[k]), ids of nconn or more and indices of nsrc or more
+        meaning "not sent"; the items sorted stably by connection (order[n]),
+        every connection's first position (conn_first[nconn + 2]; the dropped
+        items are group nconn) and optionally the descriptors in that order
+        (msgs_out[j] = msgs[order[j]]); result = {items sent, items dropped,
+        connections with an item}."""
+        self._check(self.lib.onc_group_by_conn(self.h, _ptr(rec_conn), nsrc, _ptr(via), n, nconn, _ptr(order),
+                                               _ptr(conn_first), _ptr(msgs), _ptr(msgs_out), _ptr(result)),
+                    "onc_group_by_conn")
+
+    def conn_extents(self, rec_off, nrec, conn_first, nconn, conn_off):
+        """onc_conn_extents: conn_off[c] = rec_off[min(conn_first[c], nrec)]
+        for c in 0 .. nconn + 1: connection c's bytes of the encoded stream
+        are [conn_off[c], conn_off[c + 1])."""
+        self._check(self.lib.onc_conn_extents(self.h, _ptr(rec_off), nrec, _ptr(conn_first), nconn, _ptr(conn_off)),
+                    "onc_conn_extents")
 
     def frame_streams(self, wire, seg_off, seg_len, nseg, rec_start, rec_len, rec_seg, max_records, seg_result,
                       result):
@@ -1039,6 +1061,60 @@ def match_replies_host(codec: Codec, msgs, status, rec_conn, pending, tag_out=Tr
     return {"match": raw["match"][:n], "hit": raw["hit"][:npend], "result": raw["result"][:6],
             "tag_out": None if d_tag is None else raw["tag_out"][:n],
             "still": None if d_still is None else raw["still"][:min(k, npend)], "raw": raw}
+
+
+GROUP_TILE = 1024           # ONC_GROUP_TILE: items per workgroup of onc_group_by_conn's kernels
+GROUP_CONN_MAX = 0x00FFFFFF
+
+
+def group_by_conn_host(codec: Codec, rec_conn, via, nconn, msgs=None, n=None, extra=4, device="cuda"):
+    """Convenience: the connections (uint32), an optional `via` (uint32; None:
+    item k is rec_conn[k]) and optional host descriptors (L.MSG_DTYPE, one per
+    item) -> onc_group_by_conn -> a dict of host arrays: order[n],
+    conn_first[nconn + 2], result[3], msgs_out[n] (None without msgs), and
+    `raw`: the whole output arrays with `extra` elements behind them,
+    pre-filled with sentinels (0xA5 bytes), so that a caller can see what was
+    left alone. rec_conn is uploaded with `extra` words of connection 0 behind
+    it: an item whose index is outside rec_conn and is read all the same lands
+    in group 0 instead of the dropped group."""
+    torch = _torch()
+    rc = np.ascontiguousarray(rec_conn, np.uint32)
+    nsrc = len(rc)
+    if n is None:
+        n = nsrc if via is None else len(via)
+    d_conn = _dev_words(rc, np.uint32, np.int32, device, extra=extra)
+    d_via = None if via is None else _dev_words(via, np.uint32, np.int32, device)
+    d_msgs = None if msgs is None else to_device(np.ascontiguousarray(msgs, L.MSG_DTYPE), device)
+    fill = lambda count, width: torch.full(((count + extra) * width,), 0xA5, dtype=torch.uint8, device=device)
+    order, conn_first, res = fill(n, 4), fill(nconn + 2, 8), fill(3, 8)
+    d_out = None if msgs is None else fill(n, 64)
+    codec.group_by_conn(d_conn, nsrc, d_via, n, nconn, order, conn_first, res, msgs=d_msgs, msgs_out=d_out)
+    codec.sync()
+    raw = {"order": order.cpu().numpy().view(np.uint32).copy(),
+           "conn_first": conn_first.cpu().numpy().view(np.uint64).copy(),
+           "result": res.cpu().numpy().view(np.uint64).copy(),
+           "msgs_out": None if d_out is None else d_out.cpu().numpy().copy()}
+    return {"order": raw["order"][:n], "conn_first": raw["conn_first"][:nconn + 2], "result": raw["result"][:3],
+            "msgs_out": None if d_out is None else raw["msgs_out"][:n * 64].view(L.MSG_DTYPE), "raw": raw}
+
+
+def conn_extents_host(codec: Codec, rec_off, conn_first, nconn, nrec=None, extra=4, device="cuda"):
+    """Convenience: host offsets (nrec + 1; nrec None: all but the last entry
+    of rec_off) and conn_first (nconn + 2) -> onc_conn_extents -> (conn_off[
+    nconn + 2], raw): raw is the whole output with `extra` words of 0xA5 bytes
+    behind it. rec_off is uploaded with `extra` words of 2^63 behind it, which
+    no offset equals."""
+    torch = _torch()
+    ro = np.ascontiguousarray(rec_off, np.uint64)
+    if nrec is None:
+        nrec = len(ro) - 1
+    d_ro = torch.from_numpy(np.append(ro, np.full(extra, 1 << 63, np.uint64)).view(np.int64).copy()).to(device)
+    d_cf = _dev_words(conn_first, np.uint64, np.int64, device)
+    conn_off = torch.full(((nconn + 2 + extra) * 8,), 0xA5, dtype=torch.uint8, device=device)
+    codec.conn_extents(d_ro, nrec, d_cf, nconn, conn_off)
+    codec.sync()
+    raw = conn_off.cpu().numpy().view(np.uint64).copy()
+    return raw[:nconn + 2], raw
 
 
 def place_payloads_host(codec: Codec, wire, frag_start, frag_len, rec_frag, frag_pre, rec_len, pay_pos, pay_len,
