@@ -23,7 +23,8 @@
 //                   its bytes go in `out`, where they come from, its mark
 //   defrag_copy     the hot path: a wave per 8 KiB tile of *output* (a
 //                   fragment may be empty or many MiB, so never by fragment
-//                   count), each wave a run of consecutive tiles. The
+//                   count), each wave a run of consecutive tiles: the walk
+//                   written down in tile_walk.h (walk_tiles). The
 //                   fragments that reach into the tile are staged in LDS
 //                   (found by binary search for the wave's first tile, from
 //                   the tile before after that); every 16-byte output
@@ -40,50 +41,19 @@
 #include "common.h"
 #include "defrag_plan.h"
 #include "kernels.h"
+#include "tile_walk.h"
 
 namespace onc {
 
-constexpr int kDfThreads = 256;
+constexpr int kDfThreads = kCopyThreads;
 constexpr uint64_t kDfTile = 8192;      // output bytes per wave and step
-constexpr uint32_t kDfStage = 128;      // fragments of a tile kept in LDS (more: searched in global memory)
-constexpr uint32_t kDfMaxBlocks = 2048; // defrag_copy workgroups (the tiles are dealt out among their waves)
+constexpr uint32_t kDfMaxBlocks = kCopyMaxBlocks;   // defrag_copy workgroups
 
-__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int d) {
-    const uint32_t lo = uint32_t(__shfl_up(int(uint32_t(v)), d, 64));
-    const uint32_t hi = uint32_t(__shfl_up(int(uint32_t(v >> 32)), d, 64));
-    return uint64_t(lo) | (uint64_t(hi) << 32);
-}
-__device__ __forceinline__ DefragAgg shfl_up_agg(const DefragAgg& v, int d) {
-    return DefragAgg{shfl_up_u64(v.tail, d), shfl_up_u64(v.lasts, d), shfl_up_u64(v.cnt, d), shfl_up_u64(v.has, d)};
-}
-__device__ __forceinline__ DefragAgg wave_incl_agg(DefragAgg v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const DefragAgg o = shfl_up_agg(v, d);
-        if (lane >= d) v = defrag_join(o, v);
-    }
-    return v;
-}
-// The run of the block's elements before this thread's; *total = the block.
-__device__ __forceinline__ DefragAgg block_excl_agg(const DefragAgg& v, DefragAgg* s_wave, DefragAgg* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const DefragAgg incl = wave_incl_agg(v);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    DefragAgg base = defrag_none(), sum = defrag_none();
-#pragma unroll
-    for (int w = 0; w < kDfThreads / 64; ++w) {
-        const DefragAgg t = s_wave[w];
-        if (w < wave) base = defrag_join(base, t);
-        sum = defrag_join(sum, t);
-    }
-    *total = sum;
-    __syncthreads();   // s_wave is reused by the caller's next round
-    DefragAgg prev = shfl_up_agg(incl, 1);
-    if (lane == 0) prev = defrag_none();
-    return defrag_join(base, prev);
-}
+struct DefragRun {   // the block scan's aggregate: the plan state of a run of fragments
+    using Agg = DefragAgg;
+    static __device__ __forceinline__ Agg none() { return defrag_none(); }
+    static __device__ __forceinline__ Agg join(const Agg& a, const Agg& b) { return defrag_join(a, b); }
+};
 
 struct FragElem {
     uint64_t body;
@@ -118,28 +88,16 @@ __global__ __launch_bounds__(kDfThreads) void defrag_blk_kernel(DefragArgs a) {
         // kernel launch, so a captured call is a chain of kernel nodes.
         a.lens[j] = 0;
     }
-    DefragAgg total;
-    block_excl_agg(v, s_wave, &total);
-    if (threadIdx.x == 0) a.blk[blockIdx.x] = total;
+    block_total<DefragRun>(v, s_wave, a.blk);
 }
 
 // blk[b] := the run of the blocks before b; blk[nblk] := the whole batch.
 __global__ __launch_bounds__(kDfThreads) void defrag_blkscan_kernel(DefragArgs a, uint64_t nblk) {
     __shared__ DefragAgg s_wave[kDfThreads / 64];
-    DefragAgg carry = defrag_none();
-    for (uint64_t b0 = 0; b0 < nblk; b0 += kDfThreads) {
-        const uint64_t b = b0 + threadIdx.x;
-        const DefragAgg v = b < nblk ? a.blk[b] : defrag_none();
-        DefragAgg total;
-        const DefragAgg ex = block_excl_agg(v, s_wave, &total);
-        if (b < nblk) a.blk[b] = defrag_join(carry, ex);
-        carry = defrag_join(carry, total);
-    }
-    if (threadIdx.x == 0) {
-        a.blk[nblk] = carry;
+    scan_blocks<DefragRun>(a.blk, nblk, s_wave, [&] {
         a.info[0] = 0;          // n_multi (defrag_frag adds)
         a.info[1] = ~0ull;      // the first record that does not fit starts here (defrag_place)
-    }
+    });
 }
 
 // Between this kernel and defrag_place the per-fragment arrays hold the plan:
@@ -156,7 +114,7 @@ __global__ __launch_bounds__(kDfThreads) void defrag_frag_kernel(DefragArgs a) {
         v = defrag_elem(f.body, f.last);
     }
     DefragAgg total;
-    const DefragAgg ex = defrag_join(a.blk[blockIdx.x], block_excl_agg(v, s_wave, &total));
+    const DefragAgg ex = defrag_join(a.blk[blockIdx.x], block_excl<DefragRun>(v, s_wave, &total));
     bool multi = false;
     if (j < a.nfrag) {
         a.E[j] = ex.tail;
@@ -228,17 +186,6 @@ __global__ __launch_bounds__(kDfThreads) void defrag_place_kernel(DefragArgs a) 
     }
 }
 
-// Last j in [0, n) with e[j] <= x (e[0] <= x).
-__device__ __forceinline__ uint64_t last_at_or_before(const uint64_t* e, uint64_t n, uint64_t x) {
-    uint64_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (e[mid] <= x) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // The chunks of tile [t0, t0 + kDfTile) within [D0, D1) (coordinates: bytes
 // from the 16-byte aligned address at or below the caller's out). e[0..n],
 // s / m[0..n-1]: the fragments reaching into the tile, e[0] <= the tile's
@@ -272,76 +219,30 @@ __device__ __forceinline__ void copy_tile(const uint64_t* e, const uint64_t* s, 
     }
 }
 
-// Every wave takes a run of consecutive tiles, so that only its first tile
-// searches the fragments in global memory (about 20 dependent loads: with a
-// search per tile the kernel spent a quarter of its time there). From then
-// on the tile's fragments are found in a window of kDfStage + 1 consecutive
-// entries of E staged in LDS from the previous tile's last fragment on: E is
-// sorted, so how many entries lie at or before a byte is a ballot count.
+// The walk is walk_tiles' (tile_walk.h) over the fragments' output starts E:
+// E[0] = D0 and E[nfrag] >= D1. Staged per fragment of a tile: S and M.
 __global__ __launch_bounds__(kDfThreads) void defrag_copy_kernel(DefragArgs a) {
-    __shared__ uint64_t s_e[kDfThreads / 64][kDfStage + 1];
-    __shared__ uint64_t s_s[kDfThreads / 64][kDfStage];
-    __shared__ uint32_t s_m[kDfThreads / 64][kDfStage];
-    static_assert(kDfStage == 128, "the window is staged and counted as two rounds of 64 lanes + 1");
+    __shared__ uint64_t s_e[kDfThreads / 64][kCopyStage + 1];
+    __shared__ uint64_t s_s[kDfThreads / 64][kCopyStage];
+    __shared__ uint32_t s_m[kDfThreads / 64][kCopyStage];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint64_t W = min(a.info[1], a.off[a.nfrag]);   // OK records fill [0, W), W <= out_cap
     if (W == 0) return;
     const uint64_t D0 = a.origin, D1 = a.origin + W;
-    const uint64_t ntiles = (D1 + kDfTile - 1) / kDfTile;
     const uintptr_t wire = reinterpret_cast<uintptr_t>(a.wire);
-    const uint64_t nw = uint64_t(gridDim.x) * (kDfThreads / 64);
-    const uint64_t per = (ntiles + nw - 1) / nw;
-    const uint64_t T0 = (uint64_t(blockIdx.x) * (kDfThreads / 64) + wv) * per;   // wave-uniform
-    const uint64_t T1 = min(T0 + per, ntiles);
-    if (T0 >= T1) return;
-    uint64_t* se = s_e[wv];
-    // E[0] = D0 <= lo and E[nfrag] >= D1: every search ends below nfrag.
-    // ja: a fragment with E[ja] <= the tile's first byte (kept across tiles)
-    uint64_t ja = last_at_or_before(a.E, a.nfrag + 1, max(T0 * kDfTile, D0));
-    for (uint64_t T = T0; T < T1; ++T) {
-        const uint64_t t0 = T * kDfTile;
-        const uint64_t lo = max(t0, D0), hi = min(t0 + kDfTile, D1);
-        uint32_t k, c_hi;
-        for (;;) {
-            __builtin_amdgcn_wave_barrier();   // the tile before may still read the stage
-            // (past the array the window repeats E[nfrag] >= D1: never counted)
-            const uint64_t e0 = a.E[min(ja + lane, a.nfrag)], e1 = a.E[min(ja + 64 + lane, a.nfrag)];
-            const uint64_t e2 = a.E[min(ja + kDfStage, a.nfrag)];
-            se[lane] = e0;
-            se[64 + lane] = e1;
-            if (lane == 0) se[kDfStage] = e2;
-            const uint32_t c_lo = __popcll(__ballot(e0 <= lo)) + __popcll(__ballot(e1 <= lo)) + (e2 <= lo ? 1u : 0u);
-            c_hi = __popcll(__ballot(e0 < hi)) + __popcll(__ballot(e1 < hi)) + (e2 < hi ? 1u : 0u);
-            if (c_lo == kDfStage + 1) {        // the tile starts beyond the window: search on from its end
-                ja += kDfStage;
-                ja += last_at_or_before(a.E + ja, a.nfrag + 1 - ja, lo);
-                continue;
+    walk_tiles<kDfTile>(
+        SortedArray{a.E}, a.nfrag, D0, D1, 0, s_e[wv],
+        [&](const uint64_t* e, uint64_t j0, uint32_t n, uint64_t t0, uint64_t, uint64_t) {
+            for (uint32_t i = lane; i < n; i += 64) {
+                s_s[wv][i] = a.S[j0 + i];
+                s_m[wv][i] = a.M[j0 + i];
             }
-            k = c_lo - 1;                      // window entry of the fragment holding the tile's first byte
-            if (c_hi == kDfStage + 1 && k != 0) {   // the window ends inside the tile: start it at that fragment
-                ja += k;
-                continue;
-            }
-            break;
-        }
-        if (c_hi == kDfStage + 1) {
-            // more than kDfStage fragments reach into the tile: in global memory
-            const uint64_t jb = ja + kDfStage + last_at_or_before(a.E + ja + kDfStage, a.nfrag + 1 - ja - kDfStage, hi - 1);
-            copy_tile(a.E + ja, a.S + ja, a.M + ja, jb - ja + 1, wire, a.out, t0, D0, D1, lane);
-            ja = jb;
-            continue;
-        }
-        const uint32_t n = c_hi - k;           // window entries k .. c_hi - 1 reach into the tile
-        for (uint32_t i = lane; i < n; i += 64) {
-            s_s[wv][i] = a.S[ja + k + i];
-            s_m[wv][i] = a.M[ja + k + i];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        copy_tile(se + k, s_s[wv], s_m[wv], n, wire, a.out, t0, D0, D1, lane);
-        ja += c_hi - 1;                        // the fragment holding the tile's last byte holds the next one's first or comes before it
-    }
+            wave_stage_done();
+            copy_tile(e, s_s[wv], s_m[wv], n, wire, a.out, t0, D0, D1, lane);
+        },
+        [&](uint64_t j0, uint64_t n, uint64_t t0, uint64_t, uint64_t) {
+            copy_tile(a.E + j0, a.S + j0, a.M + j0, n, wire, a.out, t0, D0, D1, lane);
+        });
 }
 
 static uint32_t df_blocks(uint64_t n) { return uint32_t((n + kDfThreads - 1) / kDfThreads); }
@@ -372,9 +273,7 @@ hipError_t launch_defrag_place(const DefragArgs& a, hipStream_t s) {
 // The grid covers the capacity (what is written is known on the device
 // only), up to kDfMaxBlocks workgroups; the kernel deals the tiles out.
 hipError_t launch_defrag_copy(const DefragArgs& a, hipStream_t s, uint32_t variant) {
-    const uint64_t per_wg = kDfTile * (kDfThreads / 64);
-    const uint64_t cap = a.out_cap > ~0ull - 16 - per_wg ? ~0ull - 16 - per_wg : a.out_cap;
-    const uint64_t wgs = (a.origin + cap + per_wg - 1) / per_wg;
+    const uint64_t wgs = copy_groups(a.origin, a.out_cap, kDfTile * (kDfThreads / 64));
     const uint64_t most = copy_max_groups(variant, kDfMaxBlocks);
     ONC_LAUNCH(defrag_copy_kernel, dim3(uint32_t(wgs < most ? wgs : most)), dim3(kDfThreads), 0, s, a);
     return hipGetLastError();

@@ -15,7 +15,8 @@
 //                  output start for the copy (E); the last record: out_off[n]
 //                  and result
 //   frag_copy      the hot path: a wave per 8 KiB tile of *output*, each wave
-//                  a run of consecutive tiles, as defrag_copy. What is staged
+//                  a run of consecutive tiles (tile_walk.h walk_tiles, as
+//                  defrag_copy). What is staged
 //                  in LDS is the *records* reaching into the tile (output
 //                  start and wire extent); inside a record the fragment of a
 //                  byte is q / (max_frag + 4), its place in it the remainder
@@ -30,46 +31,19 @@
 #include "common.h"
 #include "fragment_plan.h"
 #include "kernels.h"
+#include "tile_walk.h"
 
 namespace onc {
 
-constexpr int kFgThreads = 256;
+constexpr int kFgThreads = kCopyThreads;
 constexpr uint64_t kFgTile = 8192;      // output bytes per wave and step
-constexpr uint32_t kFgStage = 128;      // records of a tile kept in LDS (more: searched in global memory)
-constexpr uint32_t kFgMaxBlocks = 2048; // frag_copy workgroups (the tiles are dealt out among their waves)
+constexpr uint32_t kFgMaxBlocks = kCopyMaxBlocks;   // frag_copy workgroups
 
-__device__ __forceinline__ uint64_t fg_shfl_up(uint64_t v, int d) {
-    const uint32_t lo = uint32_t(__shfl_up(int(uint32_t(v)), d, 64));
-    const uint32_t hi = uint32_t(__shfl_up(int(uint32_t(v >> 32)), d, 64));
-    return uint64_t(lo) | (uint64_t(hi) << 32);
-}
-__device__ __forceinline__ FragAgg fg_shfl_up(const FragAgg& v, int d) {
-    return FragAgg{fg_shfl_up(v.bytes, d), fg_shfl_up(v.frags, d), fg_shfl_up(v.multi, d)};
-}
-// The sum of the block's elements before this thread's; *total = the block.
-__device__ __forceinline__ FragAgg fg_block_excl(const FragAgg& v, FragAgg* s_wave, FragAgg* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    FragAgg incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const FragAgg o = fg_shfl_up(incl, d);
-        if (lane >= d) incl = frag_join(o, incl);
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    FragAgg base = frag_none(), sum = frag_none();
-#pragma unroll
-    for (int w = 0; w < kFgThreads / 64; ++w) {
-        const FragAgg t = s_wave[w];
-        if (w < wave) base = frag_join(base, t);
-        sum = frag_join(sum, t);
-    }
-    *total = sum;
-    __syncthreads();   // s_wave is reused by the caller's next round
-    FragAgg prev = fg_shfl_up(incl, 1);
-    if (lane == 0) prev = frag_none();
-    return frag_join(base, prev);
-}
+struct FragSum {     // the block scan's aggregate
+    using Agg = FragAgg;
+    static __device__ __forceinline__ Agg none() { return frag_none(); }
+    static __device__ __forceinline__ Agg join(const Agg& a, const Agg& b) { return frag_join(a, b); }
+};
 
 // Record i (< n) of the trusted offsets. The wire is not read by the plan.
 __device__ __forceinline__ FragRec fg_rec(const FragmentArgs& a, uint64_t i) {
@@ -80,27 +54,15 @@ __global__ __launch_bounds__(kFgThreads) void fragp_blk_kernel(FragmentArgs a) {
     __shared__ FragAgg s_wave[kFgThreads / 64];
     const uint64_t i = uint64_t(blockIdx.x) * kFgThreads + threadIdx.x;
     const FragAgg v = i < a.n ? frag_elem(fg_rec(a, i)) : frag_none();
-    FragAgg total;
-    fg_block_excl(v, s_wave, &total);
-    if (threadIdx.x == 0) a.blk[blockIdx.x] = total;
+    block_total<FragSum>(v, s_wave, a.blk);
 }
 
 // blk[b] := the sum of the blocks before b; blk[nblk] := the whole batch.
 __global__ __launch_bounds__(kFgThreads) void fragp_blkscan_kernel(FragmentArgs a, uint64_t nblk) {
     __shared__ FragAgg s_wave[kFgThreads / 64];
-    FragAgg carry = frag_none();
-    for (uint64_t b0 = 0; b0 < nblk; b0 += kFgThreads) {
-        const uint64_t b = b0 + threadIdx.x;
-        const FragAgg v = b < nblk ? a.blk[b] : frag_none();
-        FragAgg total;
-        const FragAgg ex = fg_block_excl(v, s_wave, &total);
-        if (b < nblk) a.blk[b] = frag_join(carry, ex);
-        carry = frag_join(carry, total);
-    }
-    if (threadIdx.x == 0) {
-        a.blk[nblk] = carry;
+    scan_blocks<FragSum>(a.blk, nblk, s_wave, [&] {
         a.info[0] = ~0ull;      // the first record that does not fit starts here (fragp_apply)
-    }
+    });
 }
 
 __global__ __launch_bounds__(kFgThreads) void fragp_apply_kernel(FragmentArgs a) {
@@ -109,7 +71,7 @@ __global__ __launch_bounds__(kFgThreads) void fragp_apply_kernel(FragmentArgs a)
     FragRec r{0, 0, ONC_OK};
     if (i < a.n) r = fg_rec(a, i);
     FragAgg total;
-    const FragAgg ex = frag_join(a.blk[blockIdx.x], fg_block_excl(frag_elem(r), s_wave, &total));
+    const FragAgg ex = frag_join(a.blk[blockIdx.x], block_excl<FragSum>(frag_elem(r), s_wave, &total));
     if (i >= a.n) return;
     const uint64_t at = ex.bytes;
     a.out_off[i] = at;
@@ -128,17 +90,6 @@ __global__ __launch_bounds__(kFgThreads) void fragp_apply_kernel(FragmentArgs a)
         a.result[1] = all.bytes;
         a.result[2] = all.multi;
     }
-}
-
-// Last j in [0, n) with e[j] <= x (e[0] <= x).
-__device__ __forceinline__ uint64_t fg_last_at_or_before(const uint64_t* e, uint64_t n, uint64_t x) {
-    uint64_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (e[mid] <= x) lo = mid;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // Position q of a record whose output takes rlen bytes: a single-fragment
@@ -215,7 +166,7 @@ __device__ __forceinline__ void fg_copy_tile(const uint64_t* e, const uint64_t* 
     for (uint64_t cb = t0 + 16ull * lane; cb < t0 + kFgTile; cb += 1024) {
         if (cb + 16 <= D0 || cb >= D1) continue;
         const uint64_t b0 = max(cb, D0), b1 = min(cb + 16, D1);
-        uint64_t j = fg_last_at_or_before(e, n, b0);
+        uint64_t j = last_at_or_before(e, n, b0);
         uint64_t ej = e[j], en = e[j + 1];
         uint64_t src = ro[j] + 4, B = ro[j + 1] - ro[j] - 4;
         FragAt at = fg_at(b0 - ej, en - ej, F);
@@ -279,70 +230,28 @@ __device__ __forceinline__ void fg_copy_tile(const uint64_t* e, const uint64_t* 
     }
 }
 
-// The tiling, the run of tiles per wave and the staged window are
-// defrag_copy's (defrag.hip), over records instead of fragments: E is sorted,
-// so how many window entries lie at or before a byte is a ballot count.
+// The walk is walk_tiles' (tile_walk.h) over the records' output starts E:
+// E[0] = D0 and E[n] >= D1. Staged per record of a tile: its wire offset, and
+// the one after the last (a record's extent ends where the next one starts).
 __global__ __launch_bounds__(kFgThreads) void frag_copy_kernel(FragmentArgs a) {
-    __shared__ uint64_t s_e[kFgThreads / 64][kFgStage + 1];
-    __shared__ uint64_t s_r[kFgThreads / 64][kFgStage + 1];
-    static_assert(kFgStage == 128, "the window is staged and counted as two rounds of 64 lanes + 1");
+    __shared__ uint64_t s_e[kFgThreads / 64][kCopyStage + 1];
+    __shared__ uint64_t s_r[kFgThreads / 64][kCopyStage + 1];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint64_t W = min(a.info[0], a.E[a.n] - a.origin);   // OK records fill [0, W), W <= out_cap
     if (W == 0) return;
     const uint64_t D0 = a.origin, D1 = a.origin + W;
-    const uint64_t ntiles = (D1 + kFgTile - 1) / kFgTile;
     const uintptr_t wire = reinterpret_cast<uintptr_t>(a.wire);
-    const uint64_t nw = uint64_t(gridDim.x) * (kFgThreads / 64);
-    const uint64_t per = (ntiles + nw - 1) / nw;
-    const uint64_t T0 = (uint64_t(blockIdx.x) * (kFgThreads / 64) + wv) * per;   // wave-uniform
-    const uint64_t T1 = min(T0 + per, ntiles);
-    if (T0 >= T1) return;
-    uint64_t* se = s_e[wv];
     uint64_t* sr = s_r[wv];
-    // E[0] = D0 <= lo and E[n] >= D1: every search ends below n.
-    // ja: a record with E[ja] <= the tile's first byte (kept across tiles)
-    uint64_t ja = fg_last_at_or_before(a.E, a.n + 1, max(T0 * kFgTile, D0));
-    for (uint64_t T = T0; T < T1; ++T) {
-        const uint64_t t0 = T * kFgTile;
-        const uint64_t lo = max(t0, D0), hi = min(t0 + kFgTile, D1);
-        uint32_t k, c_hi;
-        for (;;) {
-            __builtin_amdgcn_wave_barrier();   // the tile before may still read the stage
-            // (past the array the window repeats E[n] >= D1: never counted)
-            const uint64_t e0 = a.E[min(ja + lane, a.n)], e1 = a.E[min(ja + 64 + lane, a.n)];
-            const uint64_t e2 = a.E[min(ja + kFgStage, a.n)];
-            se[lane] = e0;
-            se[64 + lane] = e1;
-            if (lane == 0) se[kFgStage] = e2;
-            const uint32_t c_lo = __popcll(__ballot(e0 <= lo)) + __popcll(__ballot(e1 <= lo)) + (e2 <= lo ? 1u : 0u);
-            c_hi = __popcll(__ballot(e0 < hi)) + __popcll(__ballot(e1 < hi)) + (e2 < hi ? 1u : 0u);
-            if (c_lo == kFgStage + 1) {        // the tile starts beyond the window: search on from its end
-                ja += kFgStage;
-                ja += fg_last_at_or_before(a.E + ja, a.n + 1 - ja, lo);
-                continue;
-            }
-            k = c_lo - 1;                      // window entry of the record holding the tile's first byte
-            if (c_hi == kFgStage + 1 && k != 0) {   // the window ends inside the tile: start it at that record
-                ja += k;
-                continue;
-            }
-            break;
-        }
-        if (c_hi == kFgStage + 1) {
-            // more than kFgStage records reach into the tile: in global memory
-            const uint64_t jb = ja + kFgStage + fg_last_at_or_before(a.E + ja + kFgStage, a.n + 1 - ja - kFgStage, hi - 1);
-            fg_copy_tile(a.E + ja, a.rec_off + ja, jb - ja + 1, a.max_frag, wire, a.out, t0, D0, D1, lane);
-            ja = jb;
-            continue;
-        }
-        const uint32_t nr = c_hi - k;          // window entries k .. c_hi - 1 reach into the tile
-        for (uint32_t i = lane; i <= nr; i += 64) sr[i] = a.rec_off[ja + k + i];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        fg_copy_tile(se + k, sr, nr, a.max_frag, wire, a.out, t0, D0, D1, lane);
-        ja += c_hi - 1;                        // the record holding the tile's last byte holds the next one's first or comes before it
-    }
+    walk_tiles<kFgTile>(
+        SortedArray{a.E}, a.n, D0, D1, 0, s_e[wv],
+        [&](const uint64_t* e, uint64_t j0, uint32_t nr, uint64_t t0, uint64_t, uint64_t) {
+            for (uint32_t i = lane; i <= nr; i += 64) sr[i] = a.rec_off[j0 + i];
+            wave_stage_done();
+            fg_copy_tile(e, sr, nr, a.max_frag, wire, a.out, t0, D0, D1, lane);
+        },
+        [&](uint64_t j0, uint64_t nr, uint64_t t0, uint64_t, uint64_t) {
+            fg_copy_tile(a.E + j0, a.rec_off + j0, nr, a.max_frag, wire, a.out, t0, D0, D1, lane);
+        });
 }
 
 static uint32_t fg_blocks(uint64_t n) { return uint32_t((n + kFgThreads - 1) / kFgThreads); }
@@ -365,9 +274,7 @@ hipError_t launch_fragp_apply(const FragmentArgs& a, hipStream_t s) {
 // The grid covers the capacity (what is written is known on the device
 // only), up to kFgMaxBlocks workgroups; the kernel deals the tiles out.
 hipError_t launch_frag_copy(const FragmentArgs& a, hipStream_t s, uint32_t variant) {
-    const uint64_t per_wg = kFgTile * (kFgThreads / 64);
-    const uint64_t cap = a.out_cap > ~0ull - 16 - per_wg ? ~0ull - 16 - per_wg : a.out_cap;
-    const uint64_t wgs = (a.origin + cap + per_wg - 1) / per_wg;
+    const uint64_t wgs = copy_groups(a.origin, a.out_cap, kFgTile * (kFgThreads / 64));
     const uint64_t most = copy_max_groups(variant, kFgMaxBlocks);
     ONC_LAUNCH(frag_copy_kernel, dim3(uint32_t(wgs < most ? wgs : most)), dim3(kFgThreads), 0, s, a);
     return hipGetLastError();

@@ -14,7 +14,8 @@
 //   place_copy   the hot path: gather_copy (gather.hip) with one more level of
 //                lookup. A wave per 8 KiB tile of `dst` (counted from the
 //                16-byte aligned address at or below it, so that every full
-//                store is aligned), each wave a run of consecutive tiles; the
+//                store is aligned), each wave a run of consecutive tiles
+//                (tile_walk.h walk_tiles); the
 //                records whose slots reach into the tile are found by one
 //                binary search of slot_off at the run's start and followed
 //                from there, and staged in LDS: slot start, body position of
@@ -38,46 +39,19 @@
 #include "defrag_heads_plan.h"
 #include "kernels.h"
 #include "payload_plan.h"
+#include "tile_walk.h"
 
 namespace onc {
 
-constexpr int kPlThreads = 256;
+constexpr int kPlThreads = kCopyThreads;
 constexpr uint64_t kPlTile = 8192;      // dst bytes per wave and step
-constexpr uint32_t kPlStage = 128;      // records of a tile kept in LDS (more: read from global memory)
-constexpr uint32_t kPlMaxBlocks = 2048; // place_copy workgroups (the tiles are dealt out among their waves)
+constexpr uint32_t kPlMaxBlocks = kCopyMaxBlocks;   // place_copy workgroups
 
-__device__ __forceinline__ uint64_t pl_shfl_up(uint64_t v, int d) {
-    const uint32_t lo = uint32_t(__shfl_up(int(uint32_t(v)), d, 64));
-    const uint32_t hi = uint32_t(__shfl_up(int(uint32_t(v >> 32)), d, 64));
-    return uint64_t(lo) | (uint64_t(hi) << 32);
-}
-__device__ __forceinline__ PayAgg pl_shfl_up(const PayAgg& v, int d) {
-    return PayAgg{pl_shfl_up(v.off, d), pl_shfl_up(v.k, d), pl_shfl_up(v.bytes, d)};
-}
-// The sum of the block's elements before this thread's; *total = the block.
-__device__ __forceinline__ PayAgg pl_block_excl(const PayAgg& v, PayAgg* s_wave, PayAgg* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    PayAgg incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const PayAgg o = pl_shfl_up(incl, d);
-        if (lane >= d) incl = payload_join(o, incl);
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    PayAgg base = payload_none(), sum = payload_none();
-#pragma unroll
-    for (int w = 0; w < kPlThreads / 64; ++w) {
-        const PayAgg t = s_wave[w];
-        if (w < wave) base = payload_join(base, t);
-        sum = payload_join(sum, t);
-    }
-    *total = sum;
-    __syncthreads();   // s_wave is reused by the caller's next round
-    PayAgg prev = pl_shfl_up(incl, 1);
-    if (lane == 0) prev = payload_none();
-    return payload_join(base, prev);
-}
+struct PaySum {      // the block scan's aggregate
+    using Agg = PayAgg;
+    static __device__ __forceinline__ Agg none() { return payload_none(); }
+    static __device__ __forceinline__ Agg join(const Agg& a, const Agg& b) { return payload_join(a, b); }
+};
 
 // Record i (< n): the descriptor's first and fourth 16 bytes hold every word
 // the slots need (xid .. call.program, then payload_len, payload_off).
@@ -101,24 +75,13 @@ __device__ __forceinline__ PayAgg pl_elem(const PaySlotsArgs& a, uint64_t i) {
 __global__ __launch_bounds__(kPlThreads) void pay_blk_kernel(PaySlotsArgs a) {
     __shared__ PayAgg s_wave[kPlThreads / 64];
     const uint64_t i = uint64_t(blockIdx.x) * kPlThreads + threadIdx.x;
-    PayAgg total;
-    pl_block_excl(pl_elem(a, i), s_wave, &total);
-    if (threadIdx.x == 0) a.blk[blockIdx.x] = total;
+    block_total<PaySum>(pl_elem(a, i), s_wave, a.blk);
 }
 
 // blk[b] := the sum of the blocks before b; blk[nblk] := the whole batch.
 __global__ __launch_bounds__(kPlThreads) void pay_blkscan_kernel(PaySlotsArgs a, uint64_t nblk) {
     __shared__ PayAgg s_wave[kPlThreads / 64];
-    PayAgg carry = payload_none();
-    for (uint64_t b0 = 0; b0 < nblk; b0 += kPlThreads) {
-        const uint64_t b = b0 + threadIdx.x;
-        const PayAgg v = b < nblk ? a.blk[b] : payload_none();
-        PayAgg total;
-        const PayAgg ex = pl_block_excl(v, s_wave, &total);
-        if (b < nblk) a.blk[b] = payload_join(carry, ex);
-        carry = payload_join(carry, total);
-    }
-    if (threadIdx.x == 0) a.blk[nblk] = carry;
+    scan_blocks<PaySum>(a.blk, nblk, s_wave, [] {});
 }
 
 // (msgs_out may be msgs: a thread reads its own descriptor whole before it
@@ -136,7 +99,7 @@ __global__ __launch_bounds__(kPlThreads) void pay_apply_kernel(PaySlotsArgs a) {
     }
     PayAgg total;
     const PayAgg ex = payload_join(a.blk[blockIdx.x],
-                                   pl_block_excl(payload_elem(m.has, m.payload_len, a.align), s_wave, &total));
+                                   block_excl<PaySum>(payload_elem(m.has, m.payload_len, a.align), s_wave, &total));
     if (i >= a.n) return;
     const uint64_t base = a.rec_start ? a.rec_start[i] : i * uint64_t(a.head_len);
     a.pay_pos[i] = m.has ? uint32_t(m.payload_off - base) : 0u;
@@ -252,28 +215,22 @@ struct PlStaged {          // in LDS
     __device__ __forceinline__ uint64_t pos(uint64_t j) const { return e[j]; }
     __device__ __forceinline__ PlRec rec(uint64_t j) const { return PlRec{lo[j], hi[j], a0[j], x0[j], v[j], r0[j]}; }
 };
-struct PlGlobal {          // more than kPlStage of them: from entry j0 on in global memory
+struct PlGlobal {          // more than kCopyStage of them: from entry j0 on in global memory
     const PlaceArgs& a;
     uint64_t j0;
     __device__ __forceinline__ uint64_t pos(uint64_t j) const { return pl_pos(a, j0 + j); }
     __device__ __forceinline__ PlRec rec(uint64_t j) const { return pl_rec(a, j0 + j); }
 };
 
-// Last j in [0, n) with pos(j) <= x (pos(0) <= x).
-template <class View>
-__device__ __forceinline__ uint64_t pl_last_at_or_before(const View& v, uint64_t n, uint64_t x) {
-    uint64_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (v.pos(mid) <= x) lo = mid;
-        else hi = mid;
+// What the walk is over: the entries' slot starts, searched among the entries
+// themselves.
+struct PlEntries {
+    const PlaceArgs& a;
+    __device__ __forceinline__ uint64_t pos(uint64_t j) const { return pl_pos(a, j); }
+    __device__ __forceinline__ uint64_t search(uint64_t j0, uint64_t n, uint64_t x) const {
+        return last_at_or_before(PlGlobal{a, j0}, n, x);
     }
-    return lo;
-}
-// ... among the entries [j0, j0 + n) themselves
-__device__ __forceinline__ uint64_t pl_search(const PlaceArgs& a, uint64_t j0, uint64_t n, uint64_t x) {
-    return pl_last_at_or_before(PlGlobal{a, j0}, n, x);
-}
+};
 
 // The chunks of tile [t0, t0 + kPlTile) within [D0, D1) (coordinates: bytes
 // from the 16-byte aligned address at or below the caller's dst; byte D of
@@ -289,7 +246,7 @@ __device__ __forceinline__ void pl_copy_tile(const PlaceArgs& a, const View& v, 
     for (uint64_t cb = t0 + 16ull * lane; cb < t0 + kPlTile; cb += 1024) {
         if (cb + 16 <= D0 || cb >= D1) continue;
         const uint64_t b0 = max(cb, D0), b1 = min(cb + 16, D1);
-        uint64_t j = pl_last_at_or_before(v, n, b0 + shift);
+        uint64_t j = last_at_or_before(v, n, b0 + shift);
         PlRec s = v.rec(j);
         const uint64_t o0 = b0 + shift - v.pos(j);
         const uint64_t P0 = b0 + shift;                       // the slot position of chunk byte i0
@@ -364,21 +321,20 @@ __device__ __forceinline__ void pl_copy_tile(const PlaceArgs& a, const View& v, 
     }
 }
 
-// The tiling, the run of tiles per wave and the staged window are
-// gather_copy's (gather.hip), over the entries' slot starts: they are sorted,
-// so how many window entries lie at or before a byte is a ballot count. A run
-// of equal starts (records without a payload) longer than the window is
-// stepped over like a tile that starts beyond it; one inside a tile sends the
-// tile to global memory like any other tile of more than kPlStage entries.
+// The walk is walk_tiles' (tile_walk.h) over the entries' slot starts:
+// pos(0) = 0 and pos(N) = 2^64 - 1 >= any end. A run of equal starts (records
+// without a payload) longer than the window is stepped over like a tile that
+// starts beyond it; one inside a tile sends the tile to global memory like any
+// other tile of more than kCopyStage entries. Staged per entry of a tile: its
+// PlRec.
 __global__ __launch_bounds__(kPlThreads) void place_copy_kernel(PlaceArgs a) {
-    __shared__ uint64_t s_e[kPlThreads / 64][kPlStage + 1];
-    __shared__ uint64_t s_lo[kPlThreads / 64][kPlStage];
-    __shared__ uint64_t s_hi[kPlThreads / 64][kPlStage];
-    __shared__ uint64_t s_a[kPlThreads / 64][kPlStage];
-    __shared__ uint32_t s_x[kPlThreads / 64][kPlStage];
-    __shared__ uint32_t s_v[kPlThreads / 64][kPlStage];
-    __shared__ uint32_t s_r[kPlThreads / 64][kPlStage];
-    static_assert(kPlStage == 128, "the window is staged and counted as two rounds of 64 lanes + 1");
+    __shared__ uint64_t s_e[kPlThreads / 64][kCopyStage + 1];
+    __shared__ uint64_t s_lo[kPlThreads / 64][kCopyStage];
+    __shared__ uint64_t s_hi[kPlThreads / 64][kCopyStage];
+    __shared__ uint64_t s_a[kPlThreads / 64][kCopyStage];
+    __shared__ uint32_t s_x[kPlThreads / 64][kCopyStage];
+    __shared__ uint32_t s_v[kPlThreads / 64][kCopyStage];
+    __shared__ uint32_t s_r[kPlThreads / 64][kCopyStage];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint64_t N = a.n + 1;                                // entries; entry N (and on) starts at 2^64 - 1
     // dst bytes [0, W) may be written: up to the last record's slice
@@ -386,67 +342,26 @@ __global__ __launch_bounds__(kPlThreads) void place_copy_kernel(PlaceArgs a) {
     if (W == 0) return;
     const uint64_t D0 = a.origin, D1 = a.origin + W;
     const uint64_t shift = 0 - a.origin;                       // (mod 2^64: D >= origin wherever it is added)
-    const uint64_t ntiles = (D1 + kPlTile - 1) / kPlTile;
-    const uint64_t nw = uint64_t(gridDim.x) * (kPlThreads / 64);
-    const uint64_t per = (ntiles + nw - 1) / nw;
-    const uint64_t T0 = (uint64_t(blockIdx.x) * (kPlThreads / 64) + wv) * per;   // wave-uniform
-    const uint64_t T1 = min(T0 + per, ntiles);
-    if (T0 >= T1) return;
-    uint64_t* se = s_e[wv];
     const uint64_t spare = uint64_t(reinterpret_cast<uintptr_t>(a.slot_off));
-    // pos(0) = 0 <= lo and pos(N) = 2^64 - 1 >= any end: every search ends below N.
-    // ja: an entry with pos(ja) <= the tile's first byte (kept across tiles)
-    uint64_t ja = pl_search(a, 0, N + 1, max(T0 * kPlTile, D0) + shift);
-    for (uint64_t T = T0; T < T1; ++T) {
-        const uint64_t t0 = T * kPlTile;
-        const uint64_t lo = max(t0, D0) + shift, hi = min(t0 + kPlTile, D1) + shift;   // slot positions
-        uint32_t k, c_hi;
-        for (;;) {
-            __builtin_amdgcn_wave_barrier();   // the tile before may still read the stage
-            // (past the last entry the window repeats pos(N) >= hi: never counted)
-            const uint64_t e0 = pl_pos(a, min(ja + lane, N)), e1 = pl_pos(a, min(ja + 64 + lane, N));
-            const uint64_t e2 = pl_pos(a, min(ja + kPlStage, N));
-            se[lane] = e0;
-            se[64 + lane] = e1;
-            if (lane == 0) se[kPlStage] = e2;
-            const uint32_t c_lo = __popcll(__ballot(e0 <= lo)) + __popcll(__ballot(e1 <= lo)) + (e2 <= lo ? 1u : 0u);
-            c_hi = __popcll(__ballot(e0 < hi)) + __popcll(__ballot(e1 < hi)) + (e2 < hi ? 1u : 0u);
-            if (c_lo == kPlStage + 1) {        // the tile starts beyond the window: search on from its end
-                ja += kPlStage;
-                ja += pl_search(a, ja, N + 1 - ja, lo);
-                continue;
+    walk_tiles<kPlTile>(
+        PlEntries{a}, N, D0, D1, shift, s_e[wv],
+        [&](const uint64_t* e, uint64_t j0, uint32_t n, uint64_t t0, uint64_t, uint64_t) {
+            for (uint32_t i = lane; i < n; i += 64) {
+                const PlRec s = pl_rec(a, j0 + i);
+                s_lo[wv][i] = s.lo;
+                s_hi[wv][i] = s.hi;
+                s_a[wv][i] = s.addr0;
+                s_x[wv][i] = s.x0;
+                s_v[wv][i] = s.vlen;
+                s_r[wv][i] = s.room0;
             }
-            k = c_lo - 1;                      // window entry of the slot holding the tile's first byte
-            if (c_hi == kPlStage + 1 && k != 0) {   // the window ends inside the tile: start it at that entry
-                ja += k;
-                continue;
-            }
-            break;
-        }
-        if (c_hi == kPlStage + 1) {
-            // more than kPlStage entries reach into the tile: in global memory
-            const uint64_t jb = ja + kPlStage + pl_search(a, ja + kPlStage, N + 1 - ja - kPlStage, hi - 1);
-            pl_copy_tile(a, PlGlobal{a, ja}, jb - ja + 1, shift, spare, a.out, t0, D0, D1, lane);
-            ja = jb;
-            continue;
-        }
-        const uint32_t n = c_hi - k;           // window entries k .. c_hi - 1 reach into the tile
-        for (uint32_t i = lane; i < n; i += 64) {
-            const PlRec s = pl_rec(a, ja + k + i);
-            s_lo[wv][i] = s.lo;
-            s_hi[wv][i] = s.hi;
-            s_a[wv][i] = s.addr0;
-            s_x[wv][i] = s.x0;
-            s_v[wv][i] = s.vlen;
-            s_r[wv][i] = s.room0;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        pl_copy_tile(a, PlStaged{se + k, s_lo[wv], s_hi[wv], s_a[wv], s_x[wv], s_v[wv], s_r[wv]}, n, shift, spare,
-                     a.out, t0, D0, D1, lane);
-        ja += c_hi - 1;                        // the entry holding the tile's last byte holds the next one's first or comes before it
-    }
+            wave_stage_done();
+            pl_copy_tile(a, PlStaged{e, s_lo[wv], s_hi[wv], s_a[wv], s_x[wv], s_v[wv], s_r[wv]}, n, shift, spare,
+                         a.out, t0, D0, D1, lane);
+        },
+        [&](uint64_t j0, uint64_t n, uint64_t t0, uint64_t, uint64_t) {
+            pl_copy_tile(a, PlGlobal{a, j0}, n, shift, spare, a.out, t0, D0, D1, lane);
+        });
 }
 
 static uint32_t pl_blocks(uint64_t n) { return uint32_t((n + kPlThreads - 1) / kPlThreads); }
@@ -474,9 +389,7 @@ hipError_t launch_pay_empty(const PaySlotsArgs& a, hipStream_t s) {
 // The grid covers the capacity (how much of it the slots use is known on the
 // device only), up to kPlMaxBlocks workgroups; the kernel deals the tiles out.
 hipError_t launch_place_copy(const PlaceArgs& a, hipStream_t s, uint32_t variant) {
-    const uint64_t per_wg = kPlTile * (kPlThreads / 64);
-    const uint64_t cap = a.dst_cap > ~0ull - 16 - per_wg ? ~0ull - 16 - per_wg : a.dst_cap;
-    const uint64_t wgs = (a.origin + cap + per_wg - 1) / per_wg;
+    const uint64_t wgs = copy_groups(a.origin, a.dst_cap, kPlTile * (kPlThreads / 64));
     const uint64_t most = copy_max_groups(variant, kPlMaxBlocks);
     ONC_LAUNCH(place_copy_kernel, dim3(uint32_t(wgs < most ? wgs : most)), dim3(kPlThreads), 0, s, a);
     return hipGetLastError();

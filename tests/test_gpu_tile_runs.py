@@ -2,8 +2,8 @@
 
 defrag_copy, frag_copy, gather_copy, place_copy and fragiov_fill deal their
 output tiles out among the waves of the grid; a wave that gets more than one
-carries its place in the sorted positions from tile to tile
-(tests/tile_walk_model.py restates that walk). The default grid has a wave per
+carries its place in the sorted positions from tile to tile (walk_tiles in
+onc-rpc_amd/csrc/tile_walk.h; tests/tile_walk_model.py restates that walk). The default grid has a wave per
 tile up to 64 MiB of output, so every other test of these kernels runs tiles
 that search for themselves. A codec made with ONC_VARIANT_COPY_ONE_GROUP
 launches the same kernels as one workgroup: 5 to 13 tiles then make runs of 2

@@ -1,4 +1,5 @@
-"""The walk model (tests/tile_walk_model.py) pinned by property, and the proof
+"""The walk model (tests/tile_walk_model.py, of walk_tiles in
+onc-rpc_amd/csrc/tile_walk.h) pinned by property, and the proof
 that every case tests/test_gpu_tile_runs.py runs reaches the outcome it is
 named for on a tile that is not the first of its wave's run — in one
 workgroup, and on no tile of the default grid. No GPU."""

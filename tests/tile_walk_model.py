@@ -6,7 +6,8 @@ put each of its outcomes on a tile that is not the first of its wave's run
 GPU).
 
 Not a test file and not product code: plain Python restating the loop written
-down above defrag_copy_kernel. A wave takes a run of `per` consecutive output
+down above walk_tiles (onc-rpc_amd/csrc/tile_walk.h), which all five kernels
+call. A wave takes a run of `per` consecutive output
 tiles. Only the run's first tile searches the sorted positions; every later
 tile starts from `ja`, the last entry the tile before handed over, and from a
 window of STAGE + 1 consecutive positions from `ja` on:
