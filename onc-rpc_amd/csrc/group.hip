@@ -48,6 +48,8 @@ constexpr int kGrDigits = int(kGroupDigits);
 constexpr int kGrFlat = 256;                   // threads of the lane-per-element kernels
 constexpr int kGrRun = kGrFlat - 1;            // conn_first entries a bounds workgroup writes per round
 static_assert(kGroupTile == ONC_GROUP_TILE, "the tile the header names");
+static_assert(kGrFlat * kGroupTile == 262144,
+              "a round of group_scan_digits: tests/test_gpu_scan_rounds.py reaches rounds two and three by it");
 static_assert(kGrDigits == kGrFlat, "the scans take a digit per thread");
 
 // The wave's active lanes of this lane's digit.

@@ -49,6 +49,8 @@ constexpr int kMtThreads = int(kMatchTile);
 constexpr int kMtWaves = kMtThreads / 64;
 constexpr int kMtClearThreads = 256;
 static_assert(kMatchTile == ONC_MATCH_TILE, "the tile the header names");
+static_assert(kMtThreads * kMatchTile == 1048576,
+              "a round of match_scan: tests/test_gpu_scan_rounds.py reaches rounds two and three by this number");
 static_assert(kMatchEmpty == ONC_MATCH_NONE, "an untouched first_rec is hit[]'s NONE");
 static_assert(sizeof(onc_pending) == 16, "moved as one 16-byte granule");
 static_assert(ONC_MATCH_MAX <= ONC_MATCH_FAILED, "an index is never a sentinel");

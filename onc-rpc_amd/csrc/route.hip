@@ -44,6 +44,8 @@ constexpr int kRtWaves = kRtThreads / 64;
 constexpr int kRtBinsMax = 256;
 constexpr int kRtScanThreads = 256;
 static_assert(kRouteTile == ONC_ROUTE_TILE, "the tile the header names");
+static_assert(kRtScanThreads * kRouteTile == 262144,
+              "a round of route_scan_bins: tests/test_gpu_scan_rounds.py reaches rounds two and three by it");
 static_assert(ONC_ROUTE_HANDLERS_MAX + 3 <= kRtBinsMax, "a bin is 8 bits");
 static_assert(ONC_ROUTE_TABLE_MAX <= kRouteTile, "the table is validated an entry per thread");
 static_assert(sizeof(onc_route) == 24, "staged as six words an entry");

@@ -10,6 +10,8 @@
 namespace onc {
 
 constexpr int kCopyThreads = 256;          // per workgroup of a plan or copy kernel: four waves
+static_assert(kCopyThreads * kCopyThreads == 65536,
+              "a round of scan_blocks: tests/test_gpu_scan_rounds.py reaches rounds two and three by this number");
 constexpr uint32_t kCopyStage = 128;       // entries of a tile kept in LDS (more: searched in global memory)
 constexpr uint32_t kCopyMaxBlocks = 2048;  // workgroups of a copy kernel (the tiles are dealt out among their waves)
 

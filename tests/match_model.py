@@ -69,3 +69,37 @@ def match(msgs, status, rec_conn, pend):
                        int((out == NOT_REPLY).sum()), int((out == FAILED).sum()), len(still)], np.uint64)
     assert int(result[:5].sum()) == n
     return {"match": out, "hit": hit, "tag_out": tag, "still": still, "result": result}
+
+
+def match_fast(msgs, status, rec_conn, pend):
+    """match without its loops, for lists and batches of a million and more:
+    the lead of a key is the first index np.unique finds for it in the list,
+    the Replies look their keys up by np.searchsorted in the sorted distinct
+    keys, and the first record that names a lead is again np.unique's first
+    index. Sorting, where the kernels hash. Held against match in
+    tests/test_match_model.py."""
+    n, npend = len(msgs), len(pend)
+    status = np.asarray(status, np.int32)
+    out = np.where(status != 0, FAILED, NOT_REPLY).astype(np.uint32)
+    hit = np.full(npend, NONE, np.uint32)
+    tag = np.zeros(n, np.uint64)
+    recs = np.flatnonzero((status == 0) & (msgs["msg_type"] == L.MSG_REPLY))
+    conn = np.zeros(n, np.uint64) if rec_conn is None else np.asarray(rec_conn, np.uint64)
+    rkey = (conn[recs] << np.uint64(32)) | msgs["xid"][recs].astype(np.uint64)
+    pkey = (pend["conn"].astype(np.uint64) << np.uint64(32)) | pend["xid"].astype(np.uint64)
+    distinct, lead = np.unique(pkey, return_index=True)
+    at = np.minimum(np.searchsorted(distinct, rkey), max(len(distinct) - 1, 0))
+    known = distinct[at] == rkey if len(distinct) else np.zeros(len(recs), bool)
+    out[recs[~known]] = UNKNOWN
+    p = lead[at[known]]                                # the lead each of these Replies names, in record order
+    named, first = np.unique(p, return_index=True)
+    out[recs[known]] = DUPLICATE
+    winners = recs[known][first]
+    out[winners] = named
+    hit[named] = winners
+    tag[winners] = pend["tag"][named]
+    still = pend[hit == NONE].copy()
+    result = np.array([int((out < FAILED).sum()), int((out == UNKNOWN).sum()), int((out == DUPLICATE).sum()),
+                       int((out == NOT_REPLY).sum()), int((out == FAILED).sum()), len(still)], np.uint64)
+    assert int(result[:5].sum()) == n
+    return {"match": out, "hit": hit, "tag_out": tag, "still": still, "result": result}

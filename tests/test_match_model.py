@@ -97,3 +97,40 @@ def test_no_records():
     _same(got, [], [NONE, NONE], [], [(1, 2, 3), (1, 2, 4)], [0, 0, 0, 0, 0, 2])
     got = _run([], None, [])
     _same(got, [], [], [], [], [0, 0, 0, 0, 0, 0])
+
+
+def test_the_fast_form_is_the_loop():
+    """match_fast (the expected value of the lists and batches of a million
+    entries in tests/test_gpu_scan_rounds.py) == match on the cases above and
+    on a batch with every outcome mixed, keys repeated in the list and in the
+    batch."""
+    def same(msgs, st, rc, pend):
+        a, b = M.match_fast(msgs, st, rc, pend), M.match(msgs, st, rc, pend)
+        assert sorted(a) == sorted(b)
+        for k in a:
+            assert a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes(), k
+        return b
+
+    T = 0xFFFFFFFF
+    hand = [([7, 7, 7], [2, 1, 3], [(1, 7, 100), (2, 7, 200), (3, 8, 300)]),
+            ([5, 6, 5], None, [(0, 5, 50), (1, 5, 51), (0, 6, 60)]),
+            ([0, T, 0, T, 1], [0, T, T, 0, 0], [(T, T, 1), (0, 0, 2), (T, 0, 3), (0, T, 4)]),
+            ([9], [4], [(4, 9, 11), (5, 1, 99), (4, 9, 22), (4, 9, 33)]),
+            ([3, 2, 2, 1, 2], [0] * 5, [(0, 1, 10), (0, 2, 20)]),
+            ([1, 2, 3], [0, 0, 0], []), ([], [], [(1, 2, 3), (1, 2, 4)]), ([], None, [])]
+    for xids, conns, rows in hand:
+        rc = None if conns is None else np.asarray(conns, np.uint32)
+        same(M.replies(xids), np.zeros(len(xids), np.int32), rc, M.pending(rows))
+    rng = np.random.default_rng(3)
+    n, npend = 4000, 1500
+    pend = np.zeros(npend, L.PENDING_DTYPE)
+    pend["conn"], pend["xid"] = rng.integers(0, 3, npend), rng.integers(0, 900, npend)
+    pend["tag"] = rng.integers(0, 1 << 64, npend, dtype=np.uint64)
+    msgs = np.frombuffer(rng.bytes(64 * n), L.MSG_DTYPE).copy()
+    msgs["xid"] = rng.integers(0, 1400, n)
+    msgs["msg_type"] = rng.choice((L.MSG_REPLY, L.MSG_REPLY, L.MSG_REPLY, L.MSG_CALL, 7), n)
+    st = np.where(rng.integers(0, 6, n) == 0, 106, 0).astype(np.int32)
+    rc = rng.integers(0, 3, n).astype(np.uint32)
+    want = same(msgs, st, rc, pend)
+    assert (want["result"] > 0).all() and len(set(zip(pend["conn"].tolist(), pend["xid"].tolist()))) < npend
+    same(msgs, st, None, pend)

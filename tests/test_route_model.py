@@ -95,3 +95,38 @@ def test_route_calls_groups_and_replies():
     assert none["result"].tolist() == [0, 0, 0, 0] and none["bin_first"].tolist() == [0] * (NH + 4)
     empty = M.route_calls(msgs, status, M.table([]), 0)         # every Call PROG_UNAVAIL
     assert empty["route"].tolist() == [0] * 7 + [1, 1, 2] and empty["result"].tolist() == [0, 7, 3, 0]
+
+
+def _same_result(a, b):
+    assert sorted(a) == sorted(b)
+    for k in a:
+        if a[k] is None:
+            assert b[k] is None, k
+        else:
+            assert a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes(), k
+
+
+def test_the_fast_form_is_the_loop():
+    """route_calls_fast (the expected value of the batches of hundreds of
+    thousands of records in tests/test_gpu_scan_rounds.py) == route_calls on
+    the cases above and on a batch with every outcome mixed."""
+    keys = [(NFS, 3, 1), (7, 7, 7), (NFS, 3, 0), (NFS, 9, 0), (NFS, 3, 1), (MOUNT, 3, 5), (NFS, 3, 5)]
+    msgs = np.concatenate([M.calls(keys, xid0=100), np.zeros(3, L.MSG_DTYPE)])
+    msgs[7]["msg_type"], msgs[7]["xid"] = L.MSG_REPLY, 55
+    msgs[8]["msg_type"] = 7
+    msgs[9]["f0"] = NFS
+    status = np.array([0] * 9 + [3], np.int32)
+    for tab, nh in ((TAB, NH), (M.table([(1, 1, 0, 0, 0, 0)]), NH), (M.table([]), 0)):
+        _same_result(M.route_calls_fast(msgs, status, tab, nh), M.route_calls(msgs, status, tab, nh))
+    _same_result(M.route_calls_fast(msgs[:0], status[:0], TAB, NH), M.route_calls(msgs[:0], status[:0], TAB, NH))
+    rng = np.random.default_rng(5)
+    n = 3000
+    m = np.frombuffer(rng.bytes(64 * n), L.MSG_DTYPE).copy()
+    st = np.where(rng.integers(0, 5, n) == 0, rng.choice((1, 10, 106, -3), n), 0).astype(np.int32)
+    m["msg_type"] = rng.choice((L.MSG_CALL, L.MSG_CALL, L.MSG_CALL, L.MSG_REPLY, 7), n)
+    m["f0"] = rng.choice((NFS, NFS, MOUNT, 100000, 0xFFFFFFFF), n)
+    m["f1"] = rng.choice((3, 3, 4, 2, 0xFFFFFFFF), n)
+    m["f2"] = rng.integers(0, 8, n)
+    want = M.route_calls(m, st, TAB, NH)
+    assert (np.bincount(want["route"], minlength=NH + 3) > 0).all() and set(want["stat"].tolist()) == {0, 1, 2, 3}
+    _same_result(M.route_calls_fast(m, st, TAB, NH), want)
