@@ -99,7 +99,10 @@ extern "C" {
  *    which adds no status code and reuses onc_defragment's timing ids;
  *    onc_group_by_conn and onc_conn_extents (a send batch grouped by
  *    connection on the device), which add no status code and reuse
- *    onc_defragment's timing ids. */
+ *    onc_defragment's timing ids; onc_xdr_unpack and onc_xdr_schema_check
+ *    with onc_xdr_field (Call arguments decoded into columns on the device),
+ *    which add no status code (the parse outcomes are the ONC_XDR_* codes of
+ *    their own array) and report under ONC_K_DEC_PARSE. */
 #define ONC_RPC_ABI_VERSION 8
 
 /* ------------------------------------------------------------------------ */
@@ -481,7 +484,9 @@ int onc_codec_sync(onc_codec* codec);
  * (under 32 bytes per pending entry plus under 1 byte per 32 records): a
  * reserve of max(n, np) covers the call. onc_group_by_conn of up to
  * max_records items keeps its digit counts and two (key, index) buffers there
- * (17 bytes per item and 7 KiB); onc_conn_extents needs no scratch. */
+ * (17 bytes per item and 7 KiB); onc_conn_extents needs no scratch.
+ * onc_xdr_unpack of up to max_records records keeps three counts per
+ * ONC_XDR_TILE records there (under 0.05 bytes per record). */
 int onc_codec_reserve(onc_codec* codec, uint64_t max_records);
 /* Map a caller's host buffer (a socket buffer: any malloc'd or mmap'd
  * range) for the kernels, so that an encode / decode reads and writes it in
@@ -564,7 +569,8 @@ int onc_abi_version(void);
  * group_bounds, group_result) under ONC_K_DEFRAG_PLAN and its scatters and
  * gather (group_identity, group_scatter, group_gather) under
  * ONC_K_DEFRAG_COPY; onc_conn_extents' one launch reports under
- * ONC_K_DEFRAG_PLAN. */
+ * ONC_K_DEFRAG_PLAN. onc_xdr_unpack reports its two launches (xdr_unpack,
+ * xdr_result) under ONC_K_DEC_PARSE. */
 #define ONC_K_ENC_LEN      0
 #define ONC_K_SCAN_TILES   1
 #define ONC_K_ENC_EMIT     2
@@ -1556,6 +1562,167 @@ int onc_route_calls(onc_codec* codec, const onc_msg* msgs, const int32_t* status
                     onc_msg*  calls_out /*[dev, n], optional*/,
                     onc_msg*  replies   /*[dev, n], optional*/,
                     uint64_t* result    /*[dev, 4]*/);
+
+/* ------------------------------------------------------------------------ */
+/* XDR of the arguments: a handler's payloads unpacked into columns          */
+/* ------------------------------------------------------------------------ */
+
+/* What a handler gets from onc_route_calls is a slice of calls_out whose
+ * payloads are still (payload_off, payload_len): an opaque run of XDR bytes
+ * (the reference stops there too: CallBody::payload() is a byte slice,
+ * src/call_body.rs:150-152). onc_xdr_unpack parses the payload of every
+ * payload-carrying record of such a slice against one flat XDR schema
+ * (RFC 4506) and writes one column per field — structure of arrays: offset[],
+ * count[], where the file handle is — a parse status per record and, when
+ * asked, the GARBAGE_ARGS answers (RFC 5531 §9) into onc_route_calls'
+ * skeletons. One handler's slice and one schema make one call.
+ *
+ * A schema is a list of at most ONC_XDR_FIELDS_MAX fields. Nested structs
+ * flatten to consecutive fields. XDR optional-data (*T, NFSv3's set_it unions,
+ * post_op_attr) is a BOOL | SELECT field followed by the fields of T, each
+ * with IF and cond_val 1; a time_how-style three-way union is a U32 | SELECT
+ * followed by arms with different cond_val. There is one selector register
+ * per record: no nesting stack, no recursion, no linked lists.
+ * Opaque and array bodies are never parsed: a column says where they are.
+ * Padding follows the reference's Opaque::from_wire (src/opaque.rs:76-95):
+ * the maximum is checked first, then the padded end against the slice; the
+ * pad bytes must be there and are not checked for zero. */
+#define ONC_XDR_FIELDS_MAX 64u
+/* type = type_flags & 0xFF */
+#define ONC_XDR_U32          0u  /* int, unsigned, enum, float bits: 4 bytes            -> u32 column              */
+#define ONC_XDR_U64          1u  /* hyper, unsigned hyper, double bits: 8 bytes, high word first -> u64 column      */
+#define ONC_XDR_BOOL         2u  /* 4 bytes, value 0 or 1                               -> u32 column              */
+#define ONC_XDR_OPAQUE_FIXED 3u  /* opaque[arg]: arg bytes + pad to 4                   -> u32 column: position    */
+#define ONC_XDR_OPAQUE_VAR   4u  /* opaque<arg>, string<arg>: length word, bytes, pad   -> n positions, then n lengths */
+#define ONC_XDR_ARRAY32      5u  /* T<arg>, 4-byte elements: count word, 4*count bytes  -> n positions, then n counts  */
+#define ONC_XDR_ARRAY64      6u  /* T<arg>, 8-byte elements                              -> likewise                */
+/* flags */
+#define ONC_XDR_SELECT    0x100u /* U32/BOOL only: the parsed value becomes the selector */
+#define ONC_XDR_IF        0x200u /* the field is on the wire only if the selector is set and == cond_val */
+#define ONC_XDR_NO_COLUMN 0x400u /* parsed and checked, nothing stored; col_off must be 0 */
+/* call flags */
+#define ONC_XDR_EXACT     0x1u   /* bytes left after the last field are an error */
+
+typedef struct onc_xdr_field {   /* 24 bytes */
+    uint32_t type_flags;
+    uint32_t arg;                /* OPAQUE_FIXED: n; OPAQUE_VAR / ARRAY*: the maximum; else 0 */
+    uint64_t col_off;            /* byte offset of the column in cols */
+    uint32_t cond_val;           /* with ONC_XDR_IF, else 0 */
+    uint32_t reserved;           /* 0 */
+} onc_xdr_field;
+
+/* xstat[r] = code | failing field << 8 (field nf for ONC_XDR_TRAILING) */
+#define ONC_XDR_OK         0u
+#define ONC_XDR_SKIPPED    1u   /* the record carries no payload (status != ONC_OK, a reply without one) */
+#define ONC_XDR_BAD_EXTENT 2u   /* the payload lies outside the wire, the head slot or the record */
+#define ONC_XDR_SHORT      3u   /* a field ends past the payload */
+#define ONC_XDR_BAD_BOOL   4u   /* a BOOL word above 1 */
+#define ONC_XDR_TOO_LONG   5u   /* a length or count above the field's maximum */
+#define ONC_XDR_TRAILING   6u   /* ONC_XDR_EXACT: bytes left after the last field */
+#define ONC_XDR_HEAD_SHORT 7u   /* heads form: a word read ends past the head (repeat with longer heads) */
+#define ONC_XDR_TILE 256u       /* records per workgroup of the kernel (tests: the sizes around it) */
+
+/* Column widths for n records: U32, BOOL and OPAQUE_FIXED take 4 n bytes; U64
+ * takes 8 n bytes, col_off a multiple of 8, the value a native uint64_t;
+ * OPAQUE_VAR and the arrays take 8 n bytes: uint32_t pos[n], then uint32_t
+ * len_or_count[n] at col_off + 4 n — the form onc_place_payloads takes as
+ * pay_pos / pay_len. All other col_off values are multiples of 4.
+ *
+ * onc_xdr_schema_check validates a schema on the host (no codec): 0, or
+ * bad + 1 where `bad` is the first field that breaks a rule; ONC_RC_EINVAL for
+ * nf > ONC_XDR_FIELDS_MAX or a NULL fields with nf > 0. The rules: the type is
+ * at most 6; no flag bits other than the three above, and reserved == 0;
+ * SELECT only on U32 or BOOL; IF only after an earlier SELECT field;
+ * cond_val == 0 without IF; arg == 0 where the type does not use it (U32, U64,
+ * BOOL); with NO_COLUMN, col_off == 0; otherwise the alignment above,
+ * col_off <= cols_cap and width * n <= cols_cap - col_off (no sum wraps), and
+ * the column's byte range overlaps no earlier field's. nf == 0 is valid. */
+int onc_xdr_schema_check(const onc_xdr_field* fields /*host*/, uint32_t nf, uint64_t n, uint64_t cols_cap);
+
+/* onc_xdr_unpack. The result is exactly this per record r:
+ *
+ *   pad4(x) = (x + 3) & ~3, in 64 bits. Every comparison below is written so that no sum wraps.
+ *   m = msgs[r]
+ *   carries = status[r] == ONC_OK and (m.msg_type == CALL or (REPLY and ACCEPTED and stat == SUCCESS))
+ *   if not carries: code = SKIPPED          # status != OK: the descriptor is not looked at at all
+ *   L = m.payload_len; o = m.payload_off
+ *   heads form (rec_start NULL, head_len != 0):
+ *       lo = r*head_len; hi = lo + head_len; base = o - lo; bad = o < lo or o > hi
+ *   else:
+ *       hi = wire_len; bad = o > wire_len or L > wire_len - o
+ *       base = rec_start ? o - rec_start[r] : 0; bad |= rec_start and o < rec_start[r]
+ *   bad |= base + L > 0xFFFFFFFF
+ *   if bad: code = BAD_EXTENT               # nothing read
+ *   p = 0; sel_ok = false
+ *   reading k bytes at p: if k > L - p: fail SHORT;
+ *                         if o + p + k > hi: fail HEAD_SHORT (heads form only)
+ *   for f in 0 .. nf-1:
+ *       if IF and not (sel_ok and sel == cond_val):      # absent
+ *           column(s)[r] = 0; if SELECT: sel_ok = false; continue
+ *       U32:   v = be32; p += 4
+ *       BOOL:  v = be32; v > 1 -> fail BAD_BOOL; p += 4
+ *       U64:   8 bytes; p += 8
+ *       OPAQUE_FIXED: pad4(arg) > L - p -> SHORT (bytes not read); pos = base + p; p += pad4(arg)
+ *       OPAQUE_VAR:   len = be32; len > arg -> TOO_LONG; pad4(len) > L - (p+4) -> SHORT;
+ *                     pos = base + p + 4; p += 4 + pad4(len)
+ *       ARRAY32/64:   c = be32; c > arg -> TOO_LONG; c*4|8 (64-bit) > L - (p+4) -> SHORT;
+ *                     pos = base + p + 4; p += 4 + bytes
+ *       present bit f set; if SELECT: sel = v; sel_ok = true
+ *   if EXACT and L - p != 0: fail TRAILING at field nf
+ *   xstat[r] = code | f_fail << 8
+ *
+ *  - The first failure wins. The failing field and every field after it write
+ *    0; `present` keeps the bits of the fields that were completed. rest_pos /
+ *    rest_len are base + p, L - p for an OK record, else 0. SKIPPED and
+ *    BAD_EXTENT records write 0 everywhere. Every element r < n of every
+ *    column is written, and nothing else of cols is.
+ *  - Positions: with rec_start (onc_decode_extents' input) they count from the
+ *    record's first byte, mark included, as onc_place_payloads' pay_pos does;
+ *    in the heads form (onc_decode_heads' descriptors) likewise, from the
+ *    record's head slot; with neither, from the payload's first byte.
+ *  - replies[dev, n] (optional, in/out): a record with msg_type == CALL and a
+ *    code of 3..6 gets replies[r].stat = ONC_ACCEPT_GARBAGE_ARGS; no other byte
+ *    of replies is written. Pass the slice of onc_route_calls' skeletons that
+ *    matches the calls_out slice. HEAD_SHORT is not patched: as after
+ *    onc_decode_heads, the caller repeats with longer heads.
+ *  - result[dev, 4] = {OK records, records with a code of 3..6, records with
+ *    any other code, 0}.
+ *  - fields[host, nf] is read before the call returns.
+ *  - The checks come before anything is launched, pointers before alignment.
+ *    ONC_RC_EINVAL: a NULL codec or result; a schema onc_xdr_schema_check
+ *    refuses; unknown call flags; both rec_start and head_len; a head_len that
+ *    onc_decode_heads would refuse; wire_len < n * head_len in the heads form;
+ *    one of rest_pos / rest_len without the other; with n > 0 a NULL wire,
+ *    msgs, status or xstat; a NULL cols when some field has a column.
+ *    ONC_RC_EALIGN: msgs or replies not 16-byte aligned; cols, present or
+ *    result not 8-byte aligned. n == 0 writes a zero result.
+ * The call is asynchronous on the codec's stream and every step is a kernel
+ * launch (a captured call replays). No atomics on caller arrays: any of them
+ * may be mapped host memory, and the receive slab normally is. Wire reads
+ * follow onc_decode's rule: only whole aligned 16-byte granules that hold at
+ * least one byte of the record's payload inside the readable window (the
+ * wire, or the head slot); nothing is read for SKIPPED and BAD_EXTENT records,
+ * and an opaque or array body only where it shares the first 80 bytes' granules
+ * with the words around it. Scratch: three counts per workgroup of
+ * ONC_XDR_TILE records, in onc_defragment's buffer: onc_codec_reserve
+ * (max_records >= n) covers it; growing it inside a capture is
+ * ONC_RC_ECAPTURE. Both launches report under ONC_K_DEC_PARSE.
+ * Kernels (xdr.hip): xdr_unpack (a lane per record; the schema travels by
+ * value in the kernel arguments, so the field loop is wave-uniform: scalar
+ * loads of the schema, uniform branches on type and flags; a lane loads the
+ * descriptor's first two 16-byte granules for an OK record only, fetches up
+ * front the granules as far as the schema's word reads can reach with every
+ * length at its maximum, five at most, and the rest on demand; a column store writes consecutive records from consecutive lanes) and
+ * xdr_result (one workgroup: the counts summed into result). The arithmetic
+ * is xdr_plan.h, shared with the host. */
+int onc_xdr_unpack(onc_codec* codec, const uint8_t* wire, uint64_t wire_len,
+                   const onc_msg* msgs, const int32_t* status, uint64_t n,
+                   const uint64_t* rec_start /*[dev, n], optional*/, uint32_t head_len /*heads form, else 0*/,
+                   const onc_xdr_field* fields /*[host, nf]: read before the call returns*/, uint32_t nf, uint32_t flags,
+                   uint8_t* cols /*[dev, cols_cap]*/, uint64_t cols_cap,
+                   uint32_t* xstat /*[dev, n]*/, uint64_t* present /*[dev, n], optional*/,
+                   uint32_t* rest_pos, uint32_t* rest_len /*[dev, n], optional, both or neither*/,
+                   onc_msg* replies /*[dev, n], optional, in/out*/, uint64_t* result /*[dev, 4]*/);
 
 /* The other half of every exchange: a client that sent Calls over many
  * connections gets their Replies back in whatever order the servers finished

@@ -2211,6 +2211,217 @@ inline RoutedCalls route_calls(Codec& codec, const std::vector<Decoded>& results
 }
 
 // ---------------------------------------------------------------------------
+// Call arguments unpacked into columns (onc_xdr_unpack)
+// ---------------------------------------------------------------------------
+// A flat XDR schema, field by field in wire order: u32() .. array64() append a
+// field; select(), when(v) and skip() qualify the field appended last.
+//   XdrSchema s;                       // NFSv3 WRITE3args
+//   s.opaque(64).u64().u32().u32().opaque(0xFFFFFFFFu);
+//   s.boolean().select().u32().when(1);    // an optional: set_it, then the value
+// layout(n) places the columns of n records itself, back to back and 8-byte
+// aligned, and checks the schema on the host (onc_xdr_schema_check): the
+// device never sees a bad one.
+class XdrSchema {
+public:
+    XdrSchema& u32() { return add(ONC_XDR_U32, 0); }
+    XdrSchema& u64() { return add(ONC_XDR_U64, 0); }
+    XdrSchema& boolean() { return add(ONC_XDR_BOOL, 0); }
+    XdrSchema& opaque_fixed(uint32_t n) { return add(ONC_XDR_OPAQUE_FIXED, n); }
+    XdrSchema& opaque(uint32_t max) { return add(ONC_XDR_OPAQUE_VAR, max); }
+    XdrSchema& array32(uint32_t max) { return add(ONC_XDR_ARRAY32, max); }
+    XdrSchema& array64(uint32_t max) { return add(ONC_XDR_ARRAY64, max); }
+    // the field's value becomes the selector of the fields that follow
+    XdrSchema& select() { return flag(ONC_XDR_SELECT); }
+    // the field is on the wire only if the selector is v
+    XdrSchema& when(uint32_t v) {
+        flag(ONC_XDR_IF);
+        fields_.back().cond_val = v;
+        return *this;
+    }
+    // parsed and checked, no column
+    XdrSchema& skip() { return flag(ONC_XDR_NO_COLUMN); }
+    size_t size() const { return fields_.size(); }
+    static uint32_t width(uint32_t type_flags) {
+        const uint32_t t = type_flags & 0xFFu;
+        return (t == ONC_XDR_U32 || t == ONC_XDR_BOOL || t == ONC_XDR_OPAQUE_FIXED) ? 4u : 8u;
+    }
+    std::vector<onc_xdr_field> layout(size_t n, uint64_t* cols_cap) const {
+        std::vector<onc_xdr_field> f = fields_;
+        uint64_t off = 0;
+        for (onc_xdr_field& e : f) {
+            if (e.type_flags & ONC_XDR_NO_COLUMN) continue;
+            e.col_off = off;
+            off += (uint64_t(width(e.type_flags)) * n + 7) & ~uint64_t(7);
+        }
+        const int bad = onc_xdr_schema_check(f.data(), uint32_t(f.size()), n, off);
+        if (bad != 0) throw CodecError("XdrSchema: field " + std::to_string(bad - 1) + " breaks a schema rule");
+        *cols_cap = off;
+        return f;
+    }
+
+private:
+    XdrSchema& add(uint32_t type, uint32_t arg) {
+        if (fields_.size() == ONC_XDR_FIELDS_MAX) throw CodecError("XdrSchema: too many fields");
+        fields_.push_back(onc_xdr_field{type, arg, 0, 0, 0});
+        return *this;
+    }
+    XdrSchema& flag(uint32_t f) {
+        if (fields_.empty()) throw CodecError("XdrSchema: no field to qualify");
+        fields_.back().type_flags |= f;
+        return *this;
+    }
+    std::vector<onc_xdr_field> fields_;
+};
+
+// What unpack_args returns: one column per field over the n records of the
+// slice, a parse status per record, and the reply descriptors with
+// GARBAGE_ARGS set for the Calls whose arguments do not parse. Positions count
+// from each payload's first byte; bytes(f, r) is the body they point at, in the
+// caller's wire.
+struct UnpackedArgs {
+    size_t n = 0;
+    std::vector<onc_xdr_field> fields;
+    std::vector<uint8_t> cols;
+    std::vector<uint32_t> xstat, rest_pos, rest_len;
+    std::vector<uint64_t> present;
+    std::vector<onc_msg> replies;              // n: the slice's skeletons, patched
+    std::vector<Bytes> payloads;               // n: where each record's arguments lie
+    size_t n_ok = 0, n_garbage = 0, n_other = 0;
+
+    uint32_t code(size_t r) const { return xstat[r] & 0xFFu; }
+    uint32_t failed_field(size_t r) const { return xstat[r] >> 8; }
+    bool ok(size_t r) const { return code(r) == ONC_XDR_OK; }
+    bool has(size_t f, size_t r) const { return (present[r] >> f) & 1u; }
+    // the column of a U32 / BOOL field (uint32_t), of a U64 field (uint64_t),
+    // or the positions of an opaque or array field (uint32_t; lengths(f): the
+    // lengths or counts)
+    template <class T>
+    const T* column(size_t f) const {
+        const onc_xdr_field& e = field(f);
+        const bool wide = (e.type_flags & 0xFFu) == ONC_XDR_U64;
+        if (wide != (sizeof(T) == 8) || (sizeof(T) != 4 && sizeof(T) != 8)) throw CodecError("UnpackedArgs: column type");
+        return reinterpret_cast<const T*>(cols.data() + e.col_off);
+    }
+    const uint32_t* lengths(size_t f) const {
+        if ((field(f).type_flags & 0xFFu) < ONC_XDR_OPAQUE_VAR) throw CodecError("UnpackedArgs: the field has no lengths");
+        return column<uint32_t>(f) + n;
+    }
+    // the body of an opaque or array field of record r (empty when the field is absent or the record failed)
+    Bytes bytes(size_t f, size_t r) const {
+        const onc_xdr_field& e = field(f);
+        const uint32_t t = e.type_flags & 0xFFu;
+        if (t < ONC_XDR_OPAQUE_FIXED) throw CodecError("UnpackedArgs: the field has no body");
+        if (!has(f, r)) return Bytes();
+        const uint32_t pos = column<uint32_t>(f)[r];
+        const uint64_t len = t == ONC_XDR_OPAQUE_FIXED ? e.arg
+                                                       : uint64_t(lengths(f)[r]) * (t == ONC_XDR_ARRAY32 ? 4u : (t == ONC_XDR_ARRAY64 ? 8u : 1u));
+        return Bytes(payloads[r].ptr + pos, size_t(len));
+    }
+
+private:
+    const onc_xdr_field& field(size_t f) const {
+        if (f >= fields.size() || (fields[f].type_flags & ONC_XDR_NO_COLUMN)) throw CodecError("UnpackedArgs: no such column");
+        return fields[f];
+    }
+};
+
+namespace detail {
+
+// onc_xdr_unpack of n payloads inside `wire` (payload-relative positions),
+// inputs and outputs through the codec's stage; one synchronisation.
+inline UnpackedArgs unpack_payloads(Codec& codec, const uint8_t* wire, size_t wire_len, const std::vector<Bytes>& payloads,
+                                    const std::vector<int32_t>& status, const onc_msg* skeletons, const XdrSchema& schema,
+                                    uint32_t flags) {
+    const size_t n = payloads.size();
+    UnpackedArgs out;
+    out.n = n;
+    out.payloads = payloads;
+    uint64_t cap = 0;
+    out.fields = schema.layout(n, &cap);
+    Carve c{codec.stage(need<uint8_t>(wire_len) + 2 * need<onc_msg>(n) + need<int32_t>(n) + need<uint8_t>(size_t(cap)) +
+                        3 * need<uint32_t>(n) + need<uint64_t>(n) + need<uint64_t>(4))};
+    const auto w = c.take<uint8_t>(wire_len);
+    const auto dm = c.take<onc_msg>(n);
+    const auto st = c.take<int32_t>(n);
+    const auto cols = c.take<uint8_t>(size_t(cap));
+    const auto xs = c.take<uint32_t>(n);
+    const auto pr = c.take<uint64_t>(n);
+    const auto rp = c.take<uint32_t>(n);
+    const auto rl = c.take<uint32_t>(n);
+    const auto rep = c.take<onc_msg>(n);
+    const auto res = c.take<uint64_t>(4);
+    if (wire_len) std::memcpy(w.host, wire, wire_len);
+    for (size_t r = 0; r < n; ++r) {
+        onc_msg& d = dm.host[r];
+        std::memset(&d, 0, sizeof(d));
+        st.host[r] = status[r];
+        if (status[r] != ONC_OK) continue;
+        const Bytes& p = payloads[r];
+        if (p.len && (p.ptr < wire || p.ptr + p.len > wire + wire_len)) throw CodecError("unpack_args: a payload outside the wire");
+        d.msg_type = ONC_MSG_CALL;
+        d.payload_len = uint32_t(p.len);
+        d.payload_off = p.len ? uint64_t(p.ptr - wire) : 0;
+    }
+    if (n && skeletons) std::memcpy(rep.host, skeletons, sizeof(onc_msg) * n);
+    else if (n) std::memset(rep.host, 0, sizeof(onc_msg) * n);
+    codec.check(onc_xdr_unpack(codec.get(), w.dev, wire_len, dm.dev, st.dev, n, nullptr, 0, out.fields.data(),
+                               uint32_t(out.fields.size()), flags, cols.dev, cap, xs.dev, pr.dev, rp.dev, rl.dev, rep.dev,
+                               res.dev),
+                "onc_xdr_unpack");
+    codec.sync();
+    out.cols.assign(cols.host, cols.host + cap);
+    out.xstat.assign(xs.host, xs.host + n);
+    out.present.assign(pr.host, pr.host + n);
+    out.rest_pos.assign(rp.host, rp.host + n);
+    out.rest_len.assign(rl.host, rl.host + n);
+    out.replies.assign(rep.host, rep.host + n);
+    out.n_ok = size_t(res.host[0]);
+    out.n_garbage = size_t(res.host[1]);
+    out.n_other = size_t(res.host[2]);
+    return out;
+}
+
+inline Bytes args_of(const Decoded& d, int32_t* status) {
+    *status = d.status;
+    if (!d.ok()) return Bytes();
+    if (const CallBody* cb = d.message->call_body()) return cb->payload();
+    *status = ONC_ERR_INVALID_MESSAGE_TYPE;     // (not a Call: skipped, as a failed record is)
+    return Bytes();
+}
+
+}  // namespace detail
+
+// The arguments of one handler's Calls (a span of route_calls' result) parsed
+// against the schema on the device. `results` and `wire` are what the span's
+// indices and the decoded payloads point into. The span's reply skeletons come
+// back with GARBAGE_ARGS (RFC 5531 §9) set where the arguments do not parse.
+inline UnpackedArgs unpack_args(Codec& codec, const uint8_t* wire, size_t wire_len, const std::vector<Decoded>& results,
+                                const RoutedCalls::Span& calls, const XdrSchema& schema, uint32_t flags = 0) {
+    std::vector<Bytes> payloads(calls.n);
+    std::vector<int32_t> status(calls.n);
+    for (size_t k = 0; k < calls.n; ++k) payloads[k] = detail::args_of(results[calls.index[k]], &status[k]);
+    return detail::unpack_payloads(codec, wire, wire_len, payloads, status, calls.replies, schema, flags);
+}
+
+// ... of every record of a decoded list (records that are no Calls, and failed
+// ones, are skipped); the replies are Success skeletons with the Calls' xids.
+inline UnpackedArgs unpack_args(Codec& codec, const uint8_t* wire, size_t wire_len, const std::vector<Decoded>& results,
+                                const XdrSchema& schema, uint32_t flags = 0) {
+    const size_t n = results.size();
+    std::vector<Bytes> payloads(n);
+    std::vector<int32_t> status(n);
+    std::vector<onc_msg> skel(n);
+    for (size_t r = 0; r < n; ++r) {
+        payloads[r] = detail::args_of(results[r], &status[r]);
+        std::memset(&skel[r], 0, sizeof(onc_msg));
+        if (status[r] != ONC_OK) continue;
+        skel[r].xid = results[r].message->xid();
+        skel[r].msg_type = ONC_MSG_REPLY;
+    }
+    return detail::unpack_payloads(codec, wire, wire_len, payloads, status, skel.data(), schema, flags);
+}
+
+// ---------------------------------------------------------------------------
 // Replies paired with the Calls they answer (onc_match_replies)
 // ---------------------------------------------------------------------------
 // A client's Calls that wait for their Replies, in the order they were sent:

@@ -1758,6 +1758,67 @@ int onc_route_calls(onc_codec* c, const onc_msg* msgs, const int32_t* status, ui
     return rc;
 }
 
+int onc_xdr_schema_check(const onc_xdr_field* fields, uint32_t nf, uint64_t n, uint64_t cols_cap) {
+    if (nf > ONC_XDR_FIELDS_MAX || (nf && !fields)) return ONC_RC_EINVAL;
+    return int(onc::xdr_schema_first_bad(fields, nf, n, cols_cap));
+}
+
+int onc_xdr_unpack(onc_codec* c, const uint8_t* wire, uint64_t wire_len, const onc_msg* msgs, const int32_t* status,
+                   uint64_t n, const uint64_t* rec_start, uint32_t head_len, const onc_xdr_field* fields, uint32_t nf,
+                   uint32_t flags, uint8_t* cols, uint64_t cols_cap, uint32_t* xstat, uint64_t* present,
+                   uint32_t* rest_pos, uint32_t* rest_len, onc_msg* replies, uint64_t* result) {
+    if (!c || !result) return ONC_RC_EINVAL;
+    if (onc_xdr_schema_check(fields, nf, n, cols_cap) != 0) return ONC_RC_EINVAL;
+    if (flags & ~uint32_t(ONC_XDR_EXACT)) return ONC_RC_EINVAL;
+    if (rec_start && head_len) return ONC_RC_EINVAL;
+    if (head_len) {
+        if (!onc::heads_len_ok(head_len)) return ONC_RC_EINVAL;
+        if (wire_len / head_len < n) return ONC_RC_EINVAL;          // wire_len < n * head_len, no product formed
+    }
+    if ((rest_pos == nullptr) != (rest_len == nullptr)) return ONC_RC_EINVAL;
+    if (n && (!wire || !msgs || !status || !xstat)) return ONC_RC_EINVAL;
+    bool any_column = false;
+    for (uint32_t f = 0; f < nf; ++f) any_column = any_column || onc::xdr_has_column(fields[f].type_flags);
+    if (any_column && !cols) return ONC_RC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(msgs) & 15) || (reinterpret_cast<uintptr_t>(replies) & 15) ||
+        (reinterpret_cast<uintptr_t>(cols) & 7) || (reinterpret_cast<uintptr_t>(present) & 7) ||
+        (reinterpret_cast<uintptr_t>(result) & 7))
+        return ONC_RC_EALIGN;
+    if (onc::xdr_tiles(n) > 0x7FFFFFFFull) return ONC_RC_EINVAL;    // (a grid's workgroups)
+    if (set_device(c) != ONC_RC_OK) return ONC_RC_EHIP;
+    onc::XdrArgs a{};
+    a.wire = wire;
+    a.wire_len = wire_len;
+    a.msgs = msgs;
+    a.status = status;
+    a.n = n;
+    a.rec_start = rec_start;
+    a.head_len = head_len;
+    a.nf = nf;
+    a.flags = flags;
+    // what a lane fetches before it parses: at most kXdrPre granules wherever the payload starts in its first one
+    a.pre_bytes = uint32_t(onc::xdr_reach(fields, nf, 16 * onc::kXdrPre - 15));
+    a.cols = cols;
+    a.xstat = xstat;
+    a.present = present;
+    a.rest_pos = rest_pos;
+    a.rest_len = rest_len;
+    a.replies = replies;
+    a.result = result;
+    a.tiles = onc::xdr_tiles(n);
+    for (uint32_t f = 0; f < nf; ++f) a.fields[f] = fields[f];
+    // onc_defragment's buffer, a record where it keeps a fragment: 12 bytes per
+    // 256 records of its 28 per fragment
+    const int rc = ensure_defrag(c, n ? n : 1);
+    if (rc != ONC_RC_OK) return rc;
+    a.counts = reinterpret_cast<uint32_t*>(c->dfr);
+    if (n) {
+        const int ru = run(c, ONC_K_DEC_PARSE, "xdr_unpack", [&] { return onc::launch_xdr_unpack(a, c->stream); });
+        if (ru != ONC_RC_OK) return ru;
+    }
+    return run(c, ONC_K_DEC_PARSE, "xdr_result", [&] { return onc::launch_xdr_result(a, c->stream); });
+}
+
 int onc_match_replies(onc_codec* c, const onc_msg* msgs, const int32_t* status, const uint32_t* rec_conn, uint64_t n,
                       const onc_pending* pending, uint64_t np, uint32_t* match, uint32_t* hit, uint64_t* tag_out,
                       onc_pending* still, uint64_t* result) {

@@ -17,6 +17,7 @@
 #include "match_plan.h"
 #include "payload_plan.h"
 #include "route_plan.h"
+#include "xdr_plan.h"
 
 namespace onc {
 
@@ -354,6 +355,33 @@ struct GroupArgs {
     const uint32_t* sorted_key; // n: the last pass's keys
 };
 
+// onc_xdr_unpack (xdr.hip). Scratch: three counts per tile (OK, codes 3..6,
+// the other codes; 4 bytes each), in onc_defragment's buffer.
+struct XdrArgs {
+    const uint8_t* wire;
+    uint64_t wire_len;
+    const onc_msg* msgs;        // n, 16-byte aligned
+    const int32_t* status;      // n
+    uint64_t n;
+    const uint64_t* rec_start;  // n, or NULL
+    uint32_t head_len;          // != 0 (with rec_start NULL): the heads form
+    uint32_t nf;                // <= ONC_XDR_FIELDS_MAX
+    uint32_t flags;             // ONC_XDR_EXACT
+    uint32_t pre_bytes;         // payload bytes a lane fetches before the parse (xdr_reach: how far the schema's
+                                // word reads can reach, at most 16 kXdrPre - 15: kXdrPre granules at any alignment)
+    uint8_t* cols;
+    uint32_t* xstat;            // n
+    uint64_t* present;          // n, optional
+    uint32_t* rest_pos;         // n, optional
+    uint32_t* rest_len;         // n, with rest_pos
+    onc_msg* replies;           // n, optional
+    uint64_t* result;           // [4]
+    uint64_t tiles;             // xdr_tiles(n)
+    uint32_t* counts;           // 3 * tiles
+    onc_xdr_field fields[ONC_XDR_FIELDS_MAX];   // by value: the field loop reads it with scalar loads
+};
+constexpr int kXdrPre = 5;      // granules a lane issues up front at most
+
 struct DecArgs {
     uint64_t n;
     const uint8_t* wire;
@@ -530,6 +558,9 @@ hipError_t launch_route_classify(const RouteArgs& a, hipStream_t s);
 hipError_t launch_route_scan_bins(const RouteArgs& a, hipStream_t s);
 hipError_t launch_route_scan_total(const RouteArgs& a, hipStream_t s);
 hipError_t launch_route_scatter(const RouteArgs& a, hipStream_t s);
+// xdr.hip
+hipError_t launch_xdr_unpack(const XdrArgs& a, hipStream_t s);
+hipError_t launch_xdr_result(const XdrArgs& a, hipStream_t s);
 // group.hip
 uint32_t group_bounds_groups(uint32_t nconn);
 hipError_t launch_group_identity(const GroupArgs& a, hipStream_t s);

@@ -108,6 +108,13 @@ PENDING_DTYPE = np.dtype({
     "offsets": [0, 4, 8],
     "itemsize": 16,
 })
+# onc_xdr_field (onc_xdr_unpack): one field of a flat XDR schema and its column
+XDR_FIELD_DTYPE = np.dtype({
+    "names": ["type_flags", "arg", "col_off", "cond_val", "reserved"],
+    "formats": ["<u4", "<u4", "<u8", "<u4", "<u4"],
+    "offsets": [0, 4, 8, 16, 20],
+    "itemsize": 24,
+})
 
 
 def pack_kind_len(kind, length):

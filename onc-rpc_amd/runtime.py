@@ -48,6 +48,7 @@ EXPORTED = [
     "onc_piece_offsets", "onc_gather_pieces",
     "onc_payload_slots", "onc_place_payloads",
     "onc_route_calls",
+    "onc_xdr_schema_check", "onc_xdr_unpack",
     "onc_match_replies",
     "onc_group_by_conn", "onc_conn_extents",
 ]
@@ -151,6 +152,9 @@ def load_library(path=LIB_PATH):
     lib.onc_payload_slots.argtypes = [vp, vp, vp, u64, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, vp]
     lib.onc_place_payloads.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp, u64]
     lib.onc_route_calls.argtypes = [vp, vp, vp, u64, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    lib.onc_xdr_schema_check.argtypes = [vp, C.c_uint32, u64, u64]
+    lib.onc_xdr_unpack.argtypes = [vp, vp, u64, vp, vp, u64, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, u64, vp, vp,
+                                   vp, vp, vp, vp]
     lib.onc_match_replies.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, vp]
     lib.onc_group_by_conn.argtypes = [vp, vp, u64, vp, u64, C.c_uint32, vp, vp, vp, vp, vp]
     lib.onc_conn_extents.argtypes = [vp, vp, u64, vp, C.c_uint32, vp]
@@ -424,6 +428,23 @@ class Codec:
         self._check(self.lib.onc_route_calls(self.h, _ptr(msgs), _ptr(status), n, _ptr(table), ntab, nh, _ptr(route),
                                              _ptr(order), _ptr(bin_first), _ptr(calls_out), _ptr(replies),
                                              _ptr(result)), "onc_route_calls")
+
+    def xdr_unpack(self, wire, wire_len, msgs, status, n, fields, cols, xstat, result, flags=0, rec_start=None,
+                   head_len=0, present=None, rest_pos=None, rest_len=None, replies=None, cols_cap=None):
+        """onc_xdr_unpack: the payload of every payload-carrying record parsed
+        against the schema `fields` (a host L.XDR_FIELD_DTYPE array) into one
+        column per field inside `cols`, a parse status per record (xstat[n]),
+        optionally the present bits, the unparsed rest and the GARBAGE_ARGS
+        patch of `replies`; result = {OK records, garbage arguments, other
+        records, 0}. `wire`: a tensor, or an int device pointer."""
+        f = np.ascontiguousarray(fields, L.XDR_FIELD_DTYPE)
+        cap = (cols.numel() * cols.element_size() if cols is not None else 0) if cols_cap is None else cols_cap
+        wptr = C.c_void_p(wire) if isinstance(wire, int) else _ptr(wire)
+        fptr = C.c_void_p(f.ctypes.data) if len(f) else None
+        self._check(self.lib.onc_xdr_unpack(self.h, wptr, wire_len, _ptr(msgs), _ptr(status), n, _ptr(rec_start),
+                                            head_len, fptr, len(f), flags, _ptr(cols), cap, _ptr(xstat),
+                                            _ptr(present), _ptr(rest_pos), _ptr(rest_len), _ptr(replies),
+                                            _ptr(result)), "onc_xdr_unpack")
 
     def match_replies(self, msgs, status, rec_conn, n, pending, npend, match, hit, result, tag_out=None, still=None):
         """onc_match_replies: every decoded record paired with the pending Call
@@ -1015,6 +1036,92 @@ def route_calls_host(codec: Codec, msgs, status, table, nh, calls_out=True, repl
             "result": raw["result"][:4],
             "calls_out": None if d_calls is None else raw["calls_out"][:n * 64].view(L.MSG_DTYPE),
             "replies": None if d_rep is None else raw["replies"][:n * 64].view(L.MSG_DTYPE), "raw": raw}
+
+
+XDR_TILE = 256              # ONC_XDR_TILE: records per workgroup of onc_xdr_unpack's kernel
+XDR_FIELDS_MAX = 64
+XDR_U32, XDR_U64, XDR_BOOL, XDR_OPAQUE_FIXED, XDR_OPAQUE_VAR, XDR_ARRAY32, XDR_ARRAY64 = range(7)
+XDR_SELECT, XDR_IF, XDR_NO_COLUMN = 0x100, 0x200, 0x400
+XDR_EXACT = 0x1
+(XDR_OK, XDR_SKIPPED, XDR_BAD_EXTENT, XDR_SHORT, XDR_BAD_BOOL, XDR_TOO_LONG, XDR_TRAILING,
+ XDR_HEAD_SHORT) = range(8)
+
+
+def xdr_col_width(type_flags):
+    """Bytes a record takes in the column of a field of this type."""
+    return 4 if (type_flags & 0xFF) in (XDR_U32, XDR_BOOL, XDR_OPAQUE_FIXED) else 8
+
+
+def xdr_schema(specs, n):
+    """(type_flags, arg, cond_val) rows -> (an L.XDR_FIELD_DTYPE array with the
+    columns of n records laid out back to back in field order, every column
+    8-byte aligned; the bytes they take). A NO_COLUMN field takes none."""
+    f = np.zeros(len(specs), L.XDR_FIELD_DTYPE)
+    off = 0
+    for i, (tf, arg, cond) in enumerate(specs):
+        f[i]["type_flags"], f[i]["arg"], f[i]["cond_val"] = tf, arg, cond
+        if not tf & XDR_NO_COLUMN:
+            f[i]["col_off"] = off
+            off += (xdr_col_width(tf) * n + 7) & ~7
+    return f, off
+
+
+def xdr_schema_check(fields, n, cols_cap):
+    """onc_xdr_schema_check: 0, the first bad field + 1, or ONC_RC_EINVAL."""
+    lib = load_library()
+    f = np.ascontiguousarray(fields, L.XDR_FIELD_DTYPE)
+    return lib.onc_xdr_schema_check(C.c_void_p(f.ctypes.data) if len(f) else None, len(f), n, cols_cap)
+
+
+def xdr_unpack_host(codec: Codec, wire, msgs, status, fields, cols_cap, flags=0, rec_start=None, head_len=0,
+                    present=True, rest=True, replies=None, wire_len=None, extra=4, device="cuda"):
+    """Convenience: a host wire (uint8 array; or a (tensor-or-int pointer,
+    wire_len) already on the device), host descriptors (L.MSG_DTYPE), statuses
+    and a schema -> onc_xdr_unpack -> a dict of host arrays: cols[cols_cap]
+    (bytes), xstat[n], present[n], rest_pos[n], rest_len[n], replies[n] (None
+    when not asked for; `replies`: the host skeletons to patch), result[4], and
+    `raw`: the whole output arrays with `extra` words (cols: 8 `extra` bytes)
+    behind them, pre-filled with sentinels (-1; cols 0xA5), so that a caller
+    can see what was left alone."""
+    torch = _torch()
+    m = np.ascontiguousarray(msgs, L.MSG_DTYPE)
+    n = len(m)
+    if isinstance(wire, np.ndarray):
+        d_wire = to_device(np.append(wire, np.zeros(16, np.uint8)), device)
+        wlen = len(wire) if wire_len is None else wire_len
+    else:
+        d_wire, wlen = wire, wire_len
+    d_msgs = to_device(m, device)
+    d_st = _dev_words(status, np.int32, np.int32, device)
+    d_rs = None if rec_start is None else _dev_words(rec_start, np.uint64, np.int64, device)
+    cols = torch.full((cols_cap + 8 * extra,), 0xA5, dtype=torch.uint8, device=device)
+    xstat = torch.full((n + extra,), -1, dtype=torch.int32, device=device)
+    d_pres = torch.full((n + extra,), -1, dtype=torch.int64, device=device) if present else None
+    d_rp = torch.full((n + extra,), -1, dtype=torch.int32, device=device) if rest else None
+    d_rl = torch.full((n + extra,), -1, dtype=torch.int32, device=device) if rest else None
+    res = torch.full((4 + extra,), -1, dtype=torch.int64, device=device)
+    d_rep = None
+    if replies is not None:
+        d_rep = torch.full(((n + extra) * 64,), 0xA5, dtype=torch.uint8, device=device)
+        if n:
+            rp = np.ascontiguousarray(replies, L.MSG_DTYPE)
+            d_rep[:n * 64] = torch.from_numpy(rp.view(np.uint8).reshape(-1).copy()).to(device)
+    codec.xdr_unpack(d_wire, wlen, d_msgs, d_st, n, fields, cols, xstat, res, flags=flags, rec_start=d_rs,
+                     head_len=head_len, present=d_pres, rest_pos=d_rp, rest_len=d_rl, replies=d_rep,
+                     cols_cap=cols_cap)
+    codec.sync()
+
+    def words(t, dt):
+        return None if t is None else t.cpu().numpy().view(dt).copy()
+    raw = {"cols": cols.cpu().numpy().copy(), "xstat": words(xstat, np.uint32), "present": words(d_pres, np.uint64),
+           "rest_pos": words(d_rp, np.uint32), "rest_len": words(d_rl, np.uint32), "result": words(res, np.uint64),
+           "replies": None if d_rep is None else d_rep.cpu().numpy().copy()}
+    return {"cols": raw["cols"][:cols_cap], "xstat": raw["xstat"][:n],
+            "present": None if d_pres is None else raw["present"][:n],
+            "rest_pos": None if d_rp is None else raw["rest_pos"][:n],
+            "rest_len": None if d_rl is None else raw["rest_len"][:n],
+            "replies": None if d_rep is None else raw["replies"][:n * 64].view(L.MSG_DTYPE),
+            "result": raw["result"][:4], "raw": raw}
 
 
 MATCH_TILE = 1024           # ONC_MATCH_TILE: records / entries per workgroup of onc_match_replies' kernels
