@@ -1737,7 +1737,7 @@ int onc_route_calls(onc_codec* c, const onc_msg* msgs, const int32_t* status, ui
     a.calls_out = calls_out;
     a.replies = replies;
     a.result = result;
-    a.tiles = onc::route_tiles(n, onc::kRouteTile);
+    a.tiles = onc::tile_count(n, onc::kRouteTile);
     // onc_defragment's buffer, a record where it keeps a fragment: the bin
     // counts, 4 (nh + 3) (n / 1024 + 2) <= 1.02 n + 2072 bytes of its 28 per
     // fragment (for at least 65536 of them: ensure_defrag's floor). No records
@@ -1914,7 +1914,7 @@ int onc_group_by_conn(onc_codec* c, const uint32_t* rec_conn, uint64_t nsrc, con
     a.msgs = msgs;
     a.msgs_out = msgs_out;
     a.result = result;
-    a.tiles = onc::group_tiles(n, onc::kGroupTile);
+    a.tiles = onc::tile_count(n, onc::kGroupTile);
     a.counts = w + l.counts;
     a.totals = w + l.totals;
     a.first = w + l.first;

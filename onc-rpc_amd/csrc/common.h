@@ -654,4 +654,12 @@ __device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t v, uint64_t* s_
     return wave_base + incl - v;
 }
 
+// The block sum alone.
+template <int NT>
+__device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t* s_wave) {
+    uint64_t total;
+    (void)block_excl_scan_u64<NT>(v, s_wave, &total);
+    return total;
+}
+
 }  // namespace onc

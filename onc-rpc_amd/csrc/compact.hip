@@ -135,8 +135,7 @@ __global__ __launch_bounds__(kCmpThreads) void compact_iov_apply_kernel(onc_iov_
         iov[i] = r;
         if (i + 1 == n && totals) totals[1] = new_off[n];
     }
-    uint64_t total;
-    block_excl_scan_u64<kCmpThreads>(hdr, s_wave, &total);
+    const uint64_t total = block_sum_u64<kCmpThreads>(hdr, s_wave);
     if (threadIdx.x == 0 && totals && total) atomicAdd(totals, static_cast<unsigned long long>(total));
 }
 

@@ -1136,8 +1136,7 @@ __global__ __launch_bounds__(256) void dlen_tiles_kernel(const uint32_t* len, ui
     const uint64_t prev4 = lane >= 4 ? prev4_all : 0;
     const uint64_t wgi = (uint64_t(blockIdx.x) * kDecLenBlk + 64ull * (threadIdx.x >> 2)) / kDecTile;
     if ((lane & 3) == 3 && wgi * kDecTile < n) tile_sum[wgi] = incl - prev4;
-    uint64_t total;
-    block_excl_scan_u64<256>(sum, s_wave, &total);
+    const uint64_t total = block_sum_u64<256>(sum, s_wave);
     if (threadIdx.x == 0) blk_sum[blockIdx.x] = total;
 }
 

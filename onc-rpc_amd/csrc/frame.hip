@@ -510,8 +510,7 @@ __global__ __launch_bounds__(256) void frame_cblk_kernel(FrameArgs a, uint64_t* 
     const uint64_t t = uint64_t(blockIdx.x) * kCntBlk + threadIdx.x;
     const uint32_t ce = cnt_eff_of(a, t, stop);
     if (t < a.nchunks) a.cnt_eff[t] = ce;
-    uint64_t total;
-    block_excl_scan_u64<256>(ce, s_wave, &total);
+    const uint64_t total = block_sum_u64<256>(ce, s_wave);
     if (threadIdx.x == 0) blk_sum[blockIdx.x] = total;
 }
 

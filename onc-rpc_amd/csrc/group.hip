@@ -1,25 +1,20 @@
 // group.hip — a send batch grouped by connection on gfx950 (onc_group_by_conn
 // and onc_conn_extents, include/onc_rpc.h): a stable least-significant-digit
 // radix sort of (key, index) pairs, key = the item's clamped connection id,
-// with 8-bit digits; each pass is route.hip's stable partition over 256 bins.
+// with 8-bit digits; each pass is partition.h's stable partition, a digit's
+// 256 values its bins.
 //
 //   group_identity     no pass (nconn == 0): order[k] = k.
 //   per pass p (group_plan.h):
-//   group_count        a workgroup per tile of kGroupTile items. Pass 0 reads
-//                      rec_conn through via and clamps; later passes read the
-//                      pairs the pass before wrote, in sequence. A wave's
-//                      lanes of one digit are found with a ballot per digit
-//                      bit, their lowest lane adds their number in LDS; the
-//                      tile's counts go to the scratch digit-major.
-//   group_scan_digits  a workgroup per digit: the digit's tile counts scanned
-//                      in place (exclusive), its total kept.
+//   group_count        the partition's count over tiles of kGroupTile items.
+//                      Pass 0 reads rec_conn through via and clamps; later
+//                      passes read the pairs the pass before wrote, in
+//                      sequence.
+//   group_scan_digits  the partition's scan, a row per digit; its total kept.
 //   group_scan_total   one workgroup: the 256 totals scanned into first[].
-//   group_scatter      a workgroup per tile: the items read again; an item's
-//                      rank among its wave's lanes of the same digit (the
-//                      ballots again), the waves' counts per digit added in
-//                      wave order on top of first[digit] + the tile's scanned
-//                      count; then the pair goes to that place. The last pass
-//                      writes the index into the caller's order.
+//   group_scatter      the partition's scatter: the items read again, and the
+//                      pair goes to its slot. The last pass writes the index
+//                      into the caller's order.
 //   group_bounds       a lane per entry of conn_first: a lower-bound binary
 //                      search of the sorted keys (32 steps at most). A
 //                      workgroup takes runs of 255 entries and the one behind
@@ -36,9 +31,9 @@
 // launch wrote. Caller arrays see plain loads and stores only.
 #include <algorithm>
 
-#include "common.h"
 #include "group_plan.h"
 #include "kernels.h"
+#include "partition.h"
 
 namespace onc {
 
@@ -51,17 +46,6 @@ static_assert(kGroupTile == ONC_GROUP_TILE, "the tile the header names");
 static_assert(kGrFlat * kGroupTile == 262144,
               "a round of group_scan_digits: tests/test_gpu_scan_rounds.py reaches rounds two and three by it");
 static_assert(kGrDigits == kGrFlat, "the scans take a digit per thread");
-
-// The wave's active lanes of this lane's digit.
-__device__ __forceinline__ uint64_t gr_peers(uint32_t digit, bool active, uint32_t nbits) {
-    uint64_t m = __ballot(active);
-    for (uint32_t k = 0; k < nbits; ++k) {
-        const bool bit = (digit >> k) & 1u;
-        const uint64_t b = __ballot(bit);
-        m &= bit ? b : ~b;
-    }
-    return m;
-}
 
 struct GrItem {
     uint32_t key, idx;
@@ -81,17 +65,16 @@ __global__ __launch_bounds__(kGrFlat) void group_identity_kernel(GroupArgs a) {
 
 __global__ __launch_bounds__(kGrThreads) void group_count_kernel(GroupArgs a) {
     __shared__ uint32_t s_cnt[kGrDigits];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t tid = threadIdx.x;
     for (uint64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {      // (one round below 2^31 items)
         if (tid < kGrDigits) s_cnt[tid] = 0;
         __syncthreads();
         const uint64_t k = tile * kGroupTile + tid;
         const bool active = k < a.n;
         const uint32_t digit = active ? group_digit(gr_item(a, k).key, a.pass) : 0u;
-        const uint64_t peers = gr_peers(digit, active, a.digit_bits);
-        if (active && (peers & ((1ull << lane) - 1)) == 0) atomicAdd(&s_cnt[digit], uint32_t(__popcll(peers)));
+        tile_count_add(s_cnt, digit, active, wave_peers(digit, active, a.digit_bits));
         __syncthreads();
-        if (tid < kGrDigits) a.counts[group_count_at(tid, tile, a.tiles)] = s_cnt[tid];
+        if (tid < kGrDigits) a.counts[bin_count_at(tid, tile, a.tiles)] = s_cnt[tid];
     }
 }
 
@@ -99,17 +82,8 @@ __global__ __launch_bounds__(kGrThreads) void group_count_kernel(GroupArgs a) {
 __global__ __launch_bounds__(kGrFlat) void group_scan_digits_kernel(GroupArgs a) {
     __shared__ uint64_t s_wave[kGrFlat / 64];
     const uint32_t digit = blockIdx.x;
-    uint64_t carry = 0;
-    for (uint64_t t0 = 0; t0 < a.tiles; t0 += kGrFlat) {
-        const uint64_t t = t0 + threadIdx.x;
-        const uint64_t at = group_count_at(digit, t, a.tiles);
-        const uint64_t v = t < a.tiles ? a.counts[at] : 0ull;
-        uint64_t total;
-        const uint64_t ex = block_excl_scan_u64<kGrFlat>(v, s_wave, &total);
-        if (t < a.tiles) a.counts[at] = uint32_t(carry + ex);      // (below n < 2^32)
-        carry += total;
-    }
-    if (threadIdx.x == 0) a.totals[digit] = uint32_t(carry);
+    const uint64_t total = scan_bin_row<kGrFlat>(a.counts + bin_count_at(digit, 0, a.tiles), a.tiles, s_wave);
+    if (threadIdx.x == 0) a.totals[digit] = uint32_t(total);       // (n < 2^32)
 }
 
 __global__ __launch_bounds__(kGrFlat) void group_scan_total_kernel(GroupArgs a) {
@@ -121,30 +95,16 @@ __global__ __launch_bounds__(kGrFlat) void group_scan_total_kernel(GroupArgs a) 
 
 __global__ __launch_bounds__(kGrThreads) void group_scatter_kernel(GroupArgs a) {
     __shared__ uint32_t s_wcnt[kGrWaves][kGrDigits];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     for (uint64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {      // (one round below 2^31 items)
         __syncthreads();        // the round before has read s_wcnt
-        for (uint32_t i = tid; i < kGrWaves * kGrDigits; i += kGrThreads) (&s_wcnt[0][0])[i] = 0;
-        __syncthreads();
         const uint64_t k = tile * kGroupTile + tid;
         const bool active = k < a.n;
         const GrItem it = active ? gr_item(a, k) : GrItem{0u, 0u};
         const uint32_t digit = active ? group_digit(it.key, a.pass) : 0u;
-        const uint64_t peers = gr_peers(digit, active, a.digit_bits);
-        const uint32_t rank = uint32_t(__popcll(peers & ((1ull << lane) - 1)));
-        if (active && rank == 0) s_wcnt[wave][digit] = uint32_t(__popcll(peers));
-        __syncthreads();
-        if (tid < kGrDigits) {
-            // where the tile's items of this digit start, then wave by wave
-            uint32_t at = a.first[tid] + a.counts[group_count_at(tid, tile, a.tiles)];
-            for (int w = 0; w < kGrWaves; ++w) {
-                const uint32_t c = s_wcnt[w][tid];
-                s_wcnt[w][tid] = at;
-                at += c;
-            }
-        }
-        __syncthreads();
-        const uint64_t j = uint64_t(s_wcnt[wave][digit]) + rank;
+        // (d: where the tile's items of digit d start)
+        const uint64_t j = scatter_slot(s_wcnt, digit, active, wave_peers(digit, active, a.digit_bits), kGrDigits,
+                                        [&](uint32_t d) { return a.first[d] + a.counts[bin_count_at(d, tile, a.tiles)]; });
         // (j >= n only if the caller's arrays changed between the count and here)
         if (active && j < a.n) {
             a.dst_key[j] = it.key;
@@ -183,8 +143,7 @@ __global__ __launch_bounds__(kGrFlat) void group_result_kernel(GroupArgs a) {
     __shared__ uint64_t s_wave[kGrFlat / 64];
     uint64_t v = 0;
     for (uint32_t g = threadIdx.x; g < a.bounds_groups; g += kGrFlat) v += a.partial[g];
-    uint64_t total;
-    (void)block_excl_scan_u64<kGrFlat>(v, s_wave, &total);
+    const uint64_t total = block_sum_u64<kGrFlat>(v, s_wave);
     if (threadIdx.x < 3) {
         const uint64_t sent = a.passes ? group_lower_bound(a.sorted_key, a.n, a.nconn) : 0ull;
         a.result[threadIdx.x] = threadIdx.x == 0 ? sent : threadIdx.x == 1 ? a.n - sent : total;

@@ -1,17 +1,16 @@
 // group_plan.h — the arithmetic of onc_group_by_conn (group.hip): the bits and
 // the radix passes a connection count needs (group_bits, group_passes), an
-// item's key (group_clamp) and its digit in a pass (group_digit), where a
-// tile's digit count lies in the scratch (group_count_at), and the scratch
-// layout (group_layout). A pass is a stable partition by one 8-bit digit, the
-// least significant first, so `passes` of them sort the keys stably. Plain
-// C++ without HIP headers, as route_plan.h: tests/cpp_group/plan_probe.cpp
-// drives it on the host.
+// item's key (group_clamp) and its digit in a pass (group_digit), and the
+// scratch layout (group_layout). A pass is a stable partition (partition.h) by
+// one 8-bit digit, the least significant first, so `passes` of them sort the
+// keys stably. Plain C++ without HIP headers, as route_plan.h:
+// tests/cpp_group/plan_probe.cpp drives it on the host.
 #pragma once
 
 #include <stdint.h>
 
 #include "../../include/onc_rpc.h"
-#include "extent.h"
+#include "partition_plan.h"
 
 namespace onc {
 
@@ -34,17 +33,11 @@ ONC_HD inline uint32_t group_clamp(uint32_t conn, uint32_t nconn) { return conn 
 ONC_HD inline uint32_t group_digit(uint32_t key, uint32_t pass) {
     return (key >> (kGroupDigitBits * pass)) & (kGroupDigits - 1);
 }
-ONC_HD inline uint64_t group_tiles(uint64_t n, uint32_t tile) { return (n + tile - 1) / tile; }
-// The scratch holds the tiles' counts digit-major: one scan over it in memory
-// order is the stable order of the items (digit, then tile, then rank).
-ONC_HD inline uint64_t group_count_at(uint32_t digit, uint64_t tile, uint64_t tiles) {
-    return uint64_t(digit) * tiles + tile;
-}
 
-// The scratch, in u32 words from its 16-byte aligned start: the counts, a
-// total and a first position per digit, the bounds kernel's partial counts,
-// then two (key, index) buffers that the passes write in turn — 16 bytes per
-// item and a byte per item of counts.
+// The scratch, in u32 words from its 16-byte aligned start: the counts (at
+// bin_count_at, a digit the bin), a total and a first position per digit, the
+// bounds kernel's partial counts, then two (key, index) buffers that the passes
+// write in turn — 16 bytes per item and a byte per item of counts.
 struct GroupLayout {
     uint64_t counts;        // kGroupDigits * tiles
     uint64_t totals;        // kGroupDigits
@@ -56,7 +49,7 @@ struct GroupLayout {
 };
 ONC_HD inline GroupLayout group_layout(uint64_t n, uint32_t tile) {
     GroupLayout l{};
-    const uint64_t tiles = group_tiles(n, tile);
+    const uint64_t tiles = tile_count(n, tile);
     const uint64_t per = (n + 3) & ~uint64_t(3);     // the buffers stay 16-byte aligned
     l.counts = 0;
     l.totals = l.counts + uint64_t(kGroupDigits) * tiles;

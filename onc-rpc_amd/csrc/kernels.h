@@ -278,8 +278,8 @@ struct PlaceArgs {
     uint64_t dst_cap;           // the caller's capacity
 };
 
-// onc_route_calls (route.hip). Scratch: the tiles' bin counts, bin-major, and
-// a total per bin (4 bytes each), in onc_defragment's buffer.
+// onc_route_calls (route.hip). Scratch: the tiles' bin counts, bin-major
+// (partition.h), and a total per bin (4 bytes each), in onc_defragment's buffer.
 struct RouteArgs {
     const onc_msg* msgs;        // n, 16-byte aligned
     const int32_t* status;      // n
@@ -293,8 +293,8 @@ struct RouteArgs {
     onc_msg* calls_out;         // n, optional
     onc_msg* replies;           // n, optional
     uint64_t* result;           // [4]
-    uint64_t tiles;             // route_tiles(n, kRouteTile)
-    uint32_t* counts;           // (nh + 3) * tiles (route_count_at)
+    uint64_t tiles;             // tile_count(n, kRouteTile)
+    uint32_t* counts;           // (nh + 3) * tiles (bin_count_at)
     uint32_t* totals;           // nh + 3
 };
 
@@ -320,12 +320,12 @@ struct MatchArgs {
     uint64_t rtiles, ptiles;    // match_tiles(n), match_tiles(np)
     uint32_t* table;            // S: a pending index, or kMatchEmpty
     uint32_t* first_rec;        // np: the lowest record that found the entry, or kMatchEmpty
-    uint32_t* rec_counts;       // kMatchClasses * rtiles (match_class_at)
+    uint32_t* rec_counts;       // kMatchClasses * rtiles (bin_count_at)
     uint32_t* pend_counts;      // ptiles: counted by match_resolve, scanned by match_scan
 };
 
 // onc_group_by_conn (group.hip). Scratch, in onc_defragment's buffer
-// (group_plan.h GroupLayout): the tiles' digit counts, a total and a first
+// (group_plan.h GroupLayout): the tiles' digit counts (partition.h), a total and a first
 // position per digit, the bounds kernel's partial counts and two (key, index)
 // buffers — 17 bytes per item.
 struct GroupArgs {
@@ -342,8 +342,8 @@ struct GroupArgs {
     const onc_msg* msgs;        // n, optional
     onc_msg* msgs_out;          // n, optional
     uint64_t* result;           // [3]
-    uint64_t tiles;             // group_tiles(n, kGroupTile)
-    uint32_t* counts;           // kGroupDigits * tiles (group_count_at)
+    uint64_t tiles;             // tile_count(n, kGroupTile)
+    uint32_t* counts;           // kGroupDigits * tiles (bin_count_at)
     uint32_t* totals;           // kGroupDigits
     uint32_t* first;            // kGroupDigits
     uint32_t* partial;          // bounds_groups

@@ -28,7 +28,7 @@
 //                  them in the same grid: hit[p] = first_rec[p]; the tile's
 //                  unanswered entries counted.
 //   match_scan     one workgroup: the pending tiles' counts scanned in place
-//                  (exclusive), the class counts summed, result.
+//                  (partition.h scan_bin_row), the class counts summed, result.
 //   match_compact  only with `still`. A lane per pending entry: its rank among
 //                  its wave's unanswered entries by a ballot, the waves' counts
 //                  added in wave order on top of the tile's scanned count; the
@@ -39,9 +39,9 @@
 // after S slots whatever the table holds. Atomics go to the scratch alone;
 // the caller's arrays see plain loads and stores. Every index that addresses
 // memory is 64-bit.
-#include "common.h"
 #include "kernels.h"
 #include "match_plan.h"
+#include "partition.h"
 
 namespace onc {
 
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(kMtThreads) void match_resolve_kernel(MatchArgs a) 
             if (lane == 0 && b) atomicAdd(&s_cnt[c], uint32_t(__popcll(b)));
         }
         __syncthreads();
-        if (tid < kMatchClasses) a.rec_counts[match_class_at(tid, blockIdx.x, a.rtiles)] = s_cnt[tid];
+        if (tid < kMatchClasses) a.rec_counts[bin_count_at(tid, blockIdx.x, a.rtiles)] = s_cnt[tid];
     } else {
         const uint64_t tile = uint64_t(blockIdx.x) - a.rtiles;
         const uint64_t p = tile * kMatchTile + tid;
@@ -168,25 +168,16 @@ __global__ __launch_bounds__(kMtThreads) void match_scan_kernel(MatchArgs a) {
     __shared__ uint64_t s_wave[kMtWaves];
     __shared__ uint64_t s_sum[kMatchClasses];
     const uint32_t tid = threadIdx.x;
-    uint64_t carry = 0;
-    for (uint64_t t0 = 0; t0 < a.ptiles; t0 += kMtThreads) {
-        const uint64_t t = t0 + tid;
-        const uint64_t v = t < a.ptiles ? a.pend_counts[t] : 0ull;
-        uint64_t total;
-        const uint64_t ex = block_excl_scan_u64<kMtThreads>(v, s_wave, &total);
-        if (t < a.ptiles) a.pend_counts[t] = uint32_t(carry + ex);     // (below np < 2^32)
-        carry += total;
-    }
+    const uint64_t waiting = scan_bin_row<kMtThreads>(a.pend_counts, a.ptiles, s_wave);    // (np < 2^32)
     for (uint32_t c = 0; c < kMatchClasses; ++c) {
         uint64_t v = 0;
-        for (uint64_t t = tid; t < a.rtiles; t += kMtThreads) v += a.rec_counts[match_class_at(c, t, a.rtiles)];
-        uint64_t total;
-        (void)block_excl_scan_u64<kMtThreads>(v, s_wave, &total);
+        for (uint64_t t = tid; t < a.rtiles; t += kMtThreads) v += a.rec_counts[bin_count_at(c, t, a.rtiles)];
+        const uint64_t total = block_sum_u64<kMtThreads>(v, s_wave);
         if (tid == 0) s_sum[c] = total;
     }
     if (tid == 0) {
         for (uint32_t c = 0; c < kMatchClasses; ++c) a.result[c] = s_sum[c];
-        a.result[kMatchClasses] = carry;
+        a.result[kMatchClasses] = waiting;
     }
 }
 

@@ -2,7 +2,7 @@
 // count of the hash table over a pending list (match_slots), the hash of a
 // (conn, xid) key and the slot a probe tries next (match_hash, match_next),
 // where the table, first_rec and the tiles' counts lie in the scratch
-// (MatchLayout, match_layout, match_class_at) and how many u32 words that is
+// (MatchLayout, match_layout) and how many u32 words that is
 // (match_scratch_words), and a record's class (match_class). The slot count
 // reaches 2^33 and every word offset is formed in 64 bits. Plain C++ without
 // HIP headers, as route_plan.h: tests/cpp_match/plan_probe.cpp drives it on
@@ -12,7 +12,7 @@
 #include <stdint.h>
 
 #include "../../include/onc_rpc.h"
-#include "extent.h"
+#include "partition_plan.h"
 
 namespace onc {
 
@@ -46,11 +46,12 @@ ONC_HD inline uint64_t match_hash(uint32_t conn, uint32_t xid, uint64_t slots, u
 }
 ONC_HD inline uint64_t match_next(uint64_t slot, uint64_t slots) { return (slot + 1) & (slots - 1); }
 
-ONC_HD inline uint64_t match_tiles(uint64_t n) { return (n + kMatchTile - 1) / kMatchTile; }
+ONC_HD inline uint64_t match_tiles(uint64_t n) { return tile_count(n, kMatchTile); }
 
 // The scratch in u32 words: the slots, first_rec (np rounded up to four words:
-// the clear stores 16 bytes), the record tiles' class counts class-major, the
-// pending tiles' unanswered counts (scanned in place by match_scan).
+// the clear stores 16 bytes), the record tiles' class counts class-major (at
+// bin_count_at from rec_counts), the pending tiles' unanswered counts (scanned
+// in place by match_scan).
 struct MatchLayout {
     uint64_t slots;         // S
     uint64_t first_rec;     // word offsets
@@ -73,10 +74,6 @@ ONC_HD inline MatchLayout match_layout(uint64_t n, uint64_t np) {
     return l;
 }
 ONC_HD inline uint64_t match_scratch_words(uint64_t n, uint64_t np) { return match_layout(n, np).words; }
-// Where record tile t's count of class c lies, from rec_counts.
-ONC_HD inline uint64_t match_class_at(uint32_t cls, uint64_t tile, uint64_t rtiles) {
-    return uint64_t(cls) * rtiles + tile;
-}
 
 // A record's class before the duplicates are told apart: 0 = an OK Reply (to
 // be probed), else its sentinel.

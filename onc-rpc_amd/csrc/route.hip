@@ -1,7 +1,8 @@
 // route.hip — decoded Calls dispatched to their handlers on gfx950
 // (onc_route_calls, include/onc_rpc.h): a stable multi-way partition of the
 // records by bin (the handlers, then rejected, not-a-Call, failed), with a
-// table lookup in front of it and a 64-byte descriptor gather behind it.
+// table lookup in front of it and a 64-byte descriptor gather behind it. The
+// partition (count, scan, scatter) is partition.h's.
 //
 //   route_classify    a workgroup per tile of kRouteTile records. The table is
 //                     staged in LDS and validated by every workgroup (an entry
@@ -11,18 +12,11 @@
 //                     status and, for an OK record only, the descriptor's
 //                     first two 16-byte granules (msg_type, program, version |
 //                     procedure); binary search of the table (route_plan.h);
-//                     route[r]. The tile's records per bin are counted in LDS
-//                     — a wave's lanes of one bin found with a ballot per bin
-//                     bit, their lowest lane adding their number — and go to
-//                     the scratch bin-major.
-//   route_scan_bins   a workgroup per bin: the bin's tile counts scanned in
-//                     place (exclusive), its total kept.
+//                     route[r]. The partition's count.
+//   route_scan_bins   the partition's scan, a row per bin; its total kept.
 //   route_scan_total  one workgroup: the totals scanned into bin_first, and
 //                     result[0 .. 2]. For a bad table: zeros.
-//   route_scatter     a workgroup per tile: route[] re-read; a record's rank
-//                     among its wave's lanes of the same bin (the ballots
-//                     again), the waves' counts per bin added in wave order on
-//                     top of bin_first[bin] + the tile's scanned count; then
+//   route_scatter     the partition's scatter over route[] re-read: slot k;
 //                     order[k], calls_out[k] (four 16-byte loads and stores)
 //                     and replies[k] (four 16-byte stores). A reply is built
 //                     from the descriptor's xid and the bin; for a rejected
@@ -33,8 +27,8 @@
 // No workgroup waits for another: the launch boundary is the only barrier
 // between them, and inside a launch every workgroup reads only what an earlier
 // launch wrote.
-#include "common.h"
 #include "kernels.h"
+#include "partition.h"
 #include "route_plan.h"
 
 namespace onc {
@@ -57,18 +51,7 @@ __device__ __forceinline__ void rt_stage(const RouteArgs& a, onc_route* s_tab) {
     for (uint32_t w = threadIdx.x; w < 6u * a.ntab; w += kRtThreads) dst[w] = gload<uint32_t>(src + 4ull * w);
 }
 
-__device__ __forceinline__ int rt_bits(uint32_t bins) { return 32 - __builtin_clz(bins - 1); }   // bins >= 3
-
-// The wave's active lanes of this lane's bin.
-__device__ __forceinline__ uint64_t rt_peers(uint32_t bin, bool active, int nbits) {
-    uint64_t m = __ballot(active);
-    for (int k = 0; k < nbits; ++k) {
-        const bool bit = (bin >> k) & 1u;
-        const uint64_t b = __ballot(bit);
-        m &= bit ? b : ~b;
-    }
-    return m;
-}
+__device__ __forceinline__ uint32_t rt_bits(uint32_t bins) { return 32u - __builtin_clz(bins - 1); }   // bins >= 3
 
 __global__ __launch_bounds__(kRtThreads) void route_classify_kernel(RouteArgs a) {
     __shared__ onc_route s_tab[ONC_ROUTE_TABLE_MAX];
@@ -100,11 +83,9 @@ __global__ __launch_bounds__(kRtThreads) void route_classify_kernel(RouteArgs a)
         bin = route_bin(st, msg_type, call, a.nh);
         a.route[r] = bin;
     }
-    const uint64_t peers = rt_peers(bin, active, rt_bits(bins));
-    const uint32_t lane = tid & 63u;
-    if (active && (peers & ((1ull << lane) - 1)) == 0) atomicAdd(&s_cnt[bin], uint32_t(__popcll(peers)));
+    tile_count_add(s_cnt, bin, active, wave_peers(bin, active, rt_bits(bins)));
     __syncthreads();
-    if (tid < bins) a.counts[route_count_at(tid, blockIdx.x, a.tiles)] = s_cnt[tid];
+    if (tid < bins) a.counts[bin_count_at(tid, blockIdx.x, a.tiles)] = s_cnt[tid];
 }
 
 // counts[bin][t] := the bin's records in the tiles before t; totals[bin].
@@ -112,17 +93,8 @@ __global__ __launch_bounds__(kRtScanThreads) void route_scan_bins_kernel(RouteAr
     __shared__ uint64_t s_wave[kRtScanThreads / 64];
     if (a.result[3] != 0) return;                                  // a bad table: nothing was counted
     const uint32_t bin = blockIdx.x;
-    uint64_t carry = 0;
-    for (uint64_t t0 = 0; t0 < a.tiles; t0 += kRtScanThreads) {
-        const uint64_t t = t0 + threadIdx.x;
-        const uint64_t at = route_count_at(bin, t, a.tiles);
-        const uint64_t v = t < a.tiles ? a.counts[at] : 0ull;
-        uint64_t total;
-        const uint64_t ex = block_excl_scan_u64<kRtScanThreads>(v, s_wave, &total);
-        if (t < a.tiles) a.counts[at] = uint32_t(carry + ex);      // (below n < 2^32)
-        carry += total;
-    }
-    if (threadIdx.x == 0) a.totals[bin] = uint32_t(carry);
+    const uint64_t total = scan_bin_row<kRtScanThreads>(a.counts + bin_count_at(bin, 0, a.tiles), a.tiles, s_wave);
+    if (threadIdx.x == 0) a.totals[bin] = uint32_t(total);         // (n < 2^32)
 }
 
 __global__ __launch_bounds__(kRtScanThreads) void route_scan_total_kernel(RouteArgs a) {
@@ -149,30 +121,16 @@ __global__ __launch_bounds__(kRtThreads) void route_scatter_kernel(RouteArgs a) 
     __shared__ onc_route s_tab[ONC_ROUTE_TABLE_MAX];
     __shared__ uint32_t s_wcnt[kRtWaves][kRtBinsMax];
     if (a.result[3] != 0) return;                                  // a bad table: nothing is written
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     const uint32_t bins = route_bins(a.nh);
-    if (a.replies) rt_stage(a, s_tab);
-    for (uint32_t i = tid; i < kRtWaves * kRtBinsMax; i += kRtThreads) (&s_wcnt[0][0])[i] = 0;
-    __syncthreads();
+    if (a.replies) rt_stage(a, s_tab);                             // (scatter_slot's barriers stand behind it)
     const uint64_t r = uint64_t(blockIdx.x) * kRouteTile + tid;
     const bool active = r < a.n;
     const uint32_t bin = active ? a.route[r] : 0u;
-    const uint64_t peers = rt_peers(bin, active, rt_bits(bins));
-    const uint32_t rank = uint32_t(__popcll(peers & ((1ull << lane) - 1)));
-    if (active && rank == 0) s_wcnt[wave][bin] = uint32_t(__popcll(peers));
-    __syncthreads();
-    if (tid < bins) {
-        // where the tile's records of this bin start, then wave by wave
-        uint32_t at = uint32_t(a.bin_first[tid]) + a.counts[route_count_at(tid, blockIdx.x, a.tiles)];
-        for (int w = 0; w < kRtWaves; ++w) {
-            const uint32_t c = s_wcnt[w][tid];
-            s_wcnt[w][tid] = at;
-            at += c;
-        }
-    }
-    __syncthreads();
+    const uint64_t k = scatter_slot(s_wcnt, bin, active, wave_peers(bin, active, rt_bits(bins)), bins, [&](uint32_t b) {
+        return uint32_t(a.bin_first[b]) + a.counts[bin_count_at(b, blockIdx.x, a.tiles)];   // bin b's start in the tile
+    });
     if (!active) return;
-    const uint64_t k = uint64_t(s_wcnt[wave][bin]) + rank;
     a.order[k] = uint32_t(r);
     if (!a.calls_out && !a.replies) return;
     const uintptr_t src = reinterpret_cast<uintptr_t>(a.msgs + r);

@@ -2,8 +2,8 @@
 // route table obeys (route_entry_ok, route_pair_ok, route_bad_at), the lookup
 // of a Call's (program, version, procedure) in it (route_key_le, route_upper,
 // route_lookup: handler or the RFC 5531 §9 rejection with its low / high), a
-// record's bin (route_bin) and where a tile's bin count lies in the scratch
-// (route_count_at). All keys are compared unsigned, word by word; no sum of a
+// record's bin (route_bin) and the scratch its partition needs
+// (route_scratch_words). All keys are compared unsigned, word by word; no sum of a
 // procedure and a count is formed in 32 bits (proc_first + proc_count may be
 // 2^32). Plain C++ without HIP headers, as payload_plan.h:
 // tests/cpp_route/plan_probe.cpp drives it on the host.
@@ -12,7 +12,7 @@
 #include <stdint.h>
 
 #include "../../include/onc_rpc.h"
-#include "extent.h"
+#include "partition_plan.h"
 
 namespace onc {
 
@@ -20,15 +20,9 @@ constexpr uint32_t kRouteTile = 1024;     // records per tile (= threads per wor
 
 // Bins: the handlers, then rejected, not-a-Call, failed.
 ONC_HD inline uint32_t route_bins(uint32_t nh) { return nh + 3; }
-ONC_HD inline uint64_t route_tiles(uint64_t n, uint32_t tile) { return (n + tile - 1) / tile; }
-// The scratch holds the tiles' counts bin-major: one scan over it in memory
-// order is the stable order of the records (bin, then tile, then rank).
-ONC_HD inline uint64_t route_count_at(uint32_t bin, uint64_t tile, uint64_t tiles) {
-    return uint64_t(bin) * tiles + tile;
-}
-// u32 words of scratch: the counts and one total per bin.
+// u32 words of scratch: the counts (at bin_count_at) and one total per bin.
 ONC_HD inline uint64_t route_scratch_words(uint64_t n, uint32_t nh, uint32_t tile) {
-    return uint64_t(route_bins(nh)) * (route_tiles(n, tile) + 1);
+    return uint64_t(route_bins(nh)) * (tile_count(n, tile) + 1);
 }
 
 // An entry's own rules.

@@ -69,8 +69,7 @@ __global__ __launch_bounds__(kTile) void len_tiles_kernel(const uint32_t* len, u
     __shared__ uint64_t s_wave[kTile / 64];
     const uint64_t i = uint64_t(blockIdx.x) * kTile + threadIdx.x;
     const uint64_t v = i < n ? len[i] : 0;
-    uint64_t total;
-    block_excl_scan_u64<kTile>(v, s_wave, &total);
+    const uint64_t total = block_sum_u64<kTile>(v, s_wave);
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 
@@ -117,8 +116,7 @@ __global__ __launch_bounds__(kTile) void lenblk_kernel(const uint32_t* len, uint
     uint64_t sum = 0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) sum += v[k];
-    uint64_t total;
-    block_excl_scan_u64<kTile>(sum, s_wave, &total);
+    const uint64_t total = block_sum_u64<kTile>(sum, s_wave);
     if (threadIdx.x == 0) blk_sum[blockIdx.x] = total;
 }
 
@@ -138,8 +136,8 @@ __global__ __launch_bounds__(kTile) void lenoff_kernel(const uint32_t* len, uint
     uint64_t sum = 0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) sum += v[k];
-    uint64_t pre_total, total;
-    block_excl_scan_u64<kTile>(pre, s_wave, &pre_total);   // the block's base
+    uint64_t total;
+    const uint64_t pre_total = block_sum_u64<kTile>(pre, s_wave);   // the block's base
     uint64_t run = base + pre_total + block_excl_scan_u64<kTile>(sum, s_wave, &total);
     if (lo + 16 <= n && (reinterpret_cast<uintptr_t>(rec_off + lo) & 15) == 0) {
         ulonglong2* dst = reinterpret_cast<ulonglong2*>(rec_off + lo);

@@ -214,9 +214,7 @@ __device__ __forceinline__ uint64_t sum_blk_stopped(const uint32_t* blk_stopped,
 #pragma unroll
         for (int k = 0; k < 8; ++k) v += i0 + uint64_t(k) * kResultWG < nblk ? w[k] : 0u;
     }
-    uint64_t stopped;
-    block_excl_scan_u64<kResultWG>(v, s_wave, &stopped);
-    return stopped;
+    return block_sum_u64<kResultWG>(v, s_wave);
 }
 
 // result = {framed, needed, segments stopped}

@@ -193,8 +193,7 @@ __global__ __launch_bounds__(kXdrThreads) void xdr_result_kernel(const uint32_t*
         for (int k = 0; k < 3; ++k) sum[k] += counts[3ull * t + k];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        uint64_t total;
-        (void)block_excl_scan_u64<kXdrThreads>(sum[k], s_wave, &total);
+        const uint64_t total = block_sum_u64<kXdrThreads>(sum[k], s_wave);
         if (threadIdx.x == 0) result[k] = total;
     }
     if (threadIdx.x == 0) result[3] = 0;

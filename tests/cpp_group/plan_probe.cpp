@@ -10,7 +10,7 @@
 //   S tile nconn nsrc nvia, then nsrc connections, then nvia via entries (nvia == 0: no via)
 //                         -> "S <order[0 .. n)> | <conn_first[0 .. nconn + 2)> | <result[0 .. 3)>": the
 //                         items sorted pass by pass through per-tile digit counts
-//                         laid out by group_count_at and scanned in memory order,
+//                         laid out by bin_count_at and scanned in memory order,
 //                         in the buffers group_layout places, at `tile` items a tile
 #include <cinttypes>
 #include <cstdint>
@@ -25,7 +25,7 @@ static void sort(uint32_t tile, uint32_t nconn, const std::vector<uint32_t>& rec
                  bool has_via) {
     const uint64_t nsrc = rec_conn.size(), n = has_via ? via.size() : nsrc;
     const GroupLayout l = group_layout(n, tile);
-    const uint64_t tiles = group_tiles(n, tile);
+    const uint64_t tiles = tile_count(n, tile);
     std::vector<uint32_t> w(l.words, 0xA5A5A5A5u), order(n, 0xFFFFFFFFu);
     const uint32_t passes = group_passes(nconn);
     const uint32_t* sorted = nullptr;
@@ -51,13 +51,13 @@ static void sort(uint32_t tile, uint32_t nconn, const std::vector<uint32_t>& rec
         uint32_t key, idx;
         for (uint64_t k = 0; k < n; ++k) {
             item(k, key, idx);
-            ++cnt[group_count_at(group_digit(key, p), k / tile, tiles)];
+            ++cnt[bin_count_at(group_digit(key, p), k / tile, tiles)];
         }
         // the scan per digit, then the scan of the totals
         for (uint32_t g = 0; g < kGroupDigits; ++g) {
             uint32_t sum = 0;
             for (uint64_t t = 0; t < tiles; ++t) {
-                const uint64_t at = group_count_at(g, t, tiles);
+                const uint64_t at = bin_count_at(g, t, tiles);
                 const uint32_t c = cnt[at];
                 cnt[at] = sum;
                 sum += c;
@@ -72,7 +72,7 @@ static void sort(uint32_t tile, uint32_t nconn, const std::vector<uint32_t>& rec
         for (uint64_t k = 0; k < n; ++k) {
             item(k, key, idx);
             const uint32_t g = group_digit(key, p);
-            const uint64_t j = uint64_t(w[l.first + g]) + cnt[group_count_at(g, k / tile, tiles)]++;
+            const uint64_t j = uint64_t(w[l.first + g]) + cnt[bin_count_at(g, k / tile, tiles)]++;
             if (j >= n) {
                 std::printf("S out of range\n");
                 return;

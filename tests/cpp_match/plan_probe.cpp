@@ -121,7 +121,7 @@ int main() {
             unsigned cls;
             unsigned long long tile, rtiles;
             if (std::scanf("%u %llu %llu", &cls, &tile, &rtiles) != 3) die("C");
-            std::printf("C %llu\n", (unsigned long long)match_class_at(cls, tile, rtiles));
+            std::printf("C %llu\n", (unsigned long long)bin_count_at(cls, tile, rtiles));
         } else if (cmd == 'H') {
             unsigned conn, xid, var;
             unsigned long long S;

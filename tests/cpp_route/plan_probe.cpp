@@ -10,7 +10,7 @@
 //   K program version procedure
 //                         -> "K <bin> <stat> <low> <high>" (a valid table)
 //   B tile n, then n bins -> "B <order[0 .. n)> | <bin_first[0 .. nh + 4)>": the records grouped
-//                         through per-tile bin counts laid out by route_count_at
+//                         through per-tile bin counts laid out by bin_count_at
 //                         and scanned in memory order, at `tile` records a tile
 #include <cinttypes>
 #include <cstdint>
@@ -27,16 +27,16 @@ static uint32_t g_nh = 0;
 static void blocks(uint32_t tile, const std::vector<uint32_t>& bin) {
     const uint64_t n = bin.size();
     const uint32_t bins = route_bins(g_nh);
-    const uint64_t tiles = route_tiles(n, tile);
+    const uint64_t tiles = tile_count(n, tile);
     std::vector<uint32_t> cnt(route_scratch_words(n, g_nh, tile), 0);
-    for (uint64_t r = 0; r < n; ++r) ++cnt[route_count_at(bin[r], r / tile, tiles)];
+    for (uint64_t r = 0; r < n; ++r) ++cnt[bin_count_at(bin[r], r / tile, tiles)];
     // one exclusive scan in memory order; a bin's first record where its row starts
     std::vector<uint64_t> first(bins + 1, 0);
     uint64_t sum = 0;
     for (uint32_t b = 0; b < bins; ++b) {
         first[b] = sum;
         for (uint64_t t = 0; t < tiles; ++t) {
-            const uint64_t at = route_count_at(b, t, tiles);
+            const uint64_t at = bin_count_at(b, t, tiles);
             const uint32_t c = cnt[at];
             cnt[at] = uint32_t(sum);
             sum += c;
@@ -44,7 +44,7 @@ static void blocks(uint32_t tile, const std::vector<uint32_t>& bin) {
     }
     first[bins] = sum;
     std::vector<uint32_t> order(n, 0xFFFFFFFFu);
-    for (uint64_t r = 0; r < n; ++r) order[cnt[route_count_at(bin[r], r / tile, tiles)]++] = uint32_t(r);
+    for (uint64_t r = 0; r < n; ++r) order[cnt[bin_count_at(bin[r], r / tile, tiles)]++] = uint32_t(r);
     std::printf("B");
     for (uint64_t k = 0; k < n; ++k) std::printf(" %u", order[k]);
     std::printf(" |");

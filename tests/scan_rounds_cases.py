@@ -13,6 +13,8 @@ counts in rounds and carries a running aggregate from a round to the next:
   onc_group_by_conn    group_scan_digits    256 tiles x 1024 items     = R_GROUP
   onc_match_replies    match_scan           1024 tiles x 1024 entries  = R_MATCH
                        (and its class sums, a stride of 1024 record tiles)
+The last three walk their rounds in one loop, scan_bin_row of
+onc-rpc_amd/csrc/partition.h, at the round lengths their own files assert.
 
 The builders here make inputs whose counts reach a second and a third round.
 The lost_carry_* functions construct, from a model's right result, what the
